@@ -6,10 +6,18 @@ rank's batch (default 4096 galaxies of 256x256 fp32 = configs[2]; 8 ranks x 4096
 SubNet (PyTorch) -> OTF + init_l2 -> 8 x [X-update / duals / V step] on the HIP engine, with the
 denoiser replaced by the identity so the timed region is exactly the hot path the engine owns
 (the ResUNet stays PyTorch per the north star; its end-to-end cost is reported separately as
-``end_to_end`` on a sample).  Inputs are synthetic (``gdeconv.synth``), weights deterministic
+``end_to_end`` on a sample, under ``--full``).  Inputs are synthetic (``gdeconv.synth``), weights deterministic
 (``gdeconv.weights``), all resident in HBM before timing.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set-up, W warm-up steps, clock settling,
+ONE timed block of exactly K steps (``value`` = galaxies of those K steps / their wall time, ``ms_per_step``
+= that wall time / K), the outputs if ``--dump-outputs`` is given, the result line.  ``--full`` adds every
+other measurement, as sub-fields of the same line: ``--blocks`` rounds of [K eager, K hipGraph-replayed,
+K profiled steps] (``value`` = the median eager block), per-kernel and roofline figures, the all-gather
+timings (N > 1), the packed-file ingest pipeline, the end-to-end sample with the ResUNet denoiser, the CPU
+baseline, and the configs[1] / configs[4] sub-lines.
 
 N > 1: under torch.distributed.run (WORLD_SIZE set) each process is one rank; without a launcher the
 process spawns the N ranks itself (``spawn_ranks``) and forwards rank 0's line.  A process group whose
@@ -236,11 +244,37 @@ def progress(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_BYTES = 48 << 20  # what --dump-outputs may write in all (every rank together)
+
+
+def dump_outputs(path, out, rank, world):
+    """--dump-outputs: the last timed step's output [N, 1, H, W] as float32 in ``path``/output.npy
+    (output_rank<r>.npy per rank when world > 1).  A batch above this rank's share of DUMP_BYTES is cut to
+    a sample of whole galaxies, drawn without replacement from numpy's default_rng(0) and kept in batch
+    order: the same galaxies in every run with the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    N = out.shape[0]
+    keep = max(1, (DUMP_BYTES // world) // (out[0].numel() * 4))
+    if keep < N:
+        idx = np.sort(np.random.default_rng(0).choice(N, size=keep, replace=False))
+        out = out[torch.from_numpy(idx).to(out.device)]
+    name = "output.npy" if world == 1 else f"output_rank{rank}.npy"
+    np.save(os.path.join(path, name), out.detach().to("cpu", torch.float32).numpy())
+
+
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=5)
-    p.add_argument("--blocks", type=int, default=3, help="timed blocks of --steps steps (value = the median block)")
+    p.add_argument("--blocks", type=int, default=3,
+                   help="--full only: timed blocks of --steps steps (value = the median block); a plain run times one")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: hipGraph replay, per-kernel / roofline "
+                        "figures, all-gather, ingest, end-to-end, the CPU baseline, the configs[1] / configs[4] sub-lines")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the last timed step's output to DIR/output.npy (float32; "
+                        "DIR/output_rank<r>.npy per rank when N > 1): whole galaxies of the batch, a fixed seeded "
+                        "sample of them when the batch is larger than the 48 MiB the dump may take")
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--batch", type=int, default=4096, help="galaxies per GPU")
     p.add_argument("--size", type=int, default=256)
@@ -273,7 +307,12 @@ def parse():
     p.add_argument("--traffic-json", default=None,
                    help="rocprofv3 --pmc summary (per-kernel HBM bytes) for the roofline 'traffic' field "
                         "(default: profiles/pmc_traffic.json, _48 / _rl variants for those workloads)")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:
+        # a plain run: one timed block and none of the side measurements
+        args.blocks = 1
+        args.no_graph = args.no_ingest = args.no_e2e = args.no_cpu_baseline = args.no_extra = True
+    return args
 
 
 def build_model(n_iters, llh, dev, seed=1234):
@@ -405,7 +444,7 @@ def main():
                           ("configs4", dict(workload="rl", batch=4096, size=256, n_iters=100, steps=args.steps,
                                             warmup=min(2, args.warmup), settle_s=1.0, no_ingest=True, no_e2e=True,
                                             no_graph=True, cpu_sample=4))):
-            sub = argparse.Namespace(**{**vars(args), **over, "traffic_json": None})
+            sub = argparse.Namespace(**{**vars(args), **over, "traffic_json": None, "dump_outputs": None})
             torch.cuda.empty_cache()
             rec[key] = measure(sub, ctx)
     if rank == 0:
@@ -523,7 +562,8 @@ def measure(args, ctx):
         # B timed blocks of exactly K steps each; after every eager block (no profiling events: value's blocks) the
         # same window runs K replayed steps (if graphed) and K steps with the library's HIP events on (per operation
         # on the caller's stream, per launch too when nothing is pipelined: the roofline's launch durations).
-        # value = the MEDIAN eager block; every block is recorded.
+        # value = the MEDIAN eager block; every block is recorded.  A plain run (no --full) times ONE eager block
+        # of K steps and neither replays nor profiles.
         _lib.profile_enable(0)
         _lib.profile_reset()
         prof_level = 1 if chunk_bytes > 0 else 2
@@ -535,20 +575,23 @@ def measure(args, ctx):
             if gf is not None:
                 t_, gout = timed(gf.replay)
                 tg_blocks.append(t_)
-            tp_blocks.append(timed(step, prof_level)[0])
-        kstats = _lib.profile_collect()
+            if args.full:
+                tp_blocks.append(timed(step, prof_level)[0])
+        kstats = _lib.profile_collect() if args.full else {}
         assert torch.isfinite(out).all(), "non-finite output"
 
     med = lambda xs: sorted(xs)[len(xs) // 2]  # noqa: E731
     elapsed = med(te_blocks)
-    tp = med(tp_blocks)
+    tp = med(tp_blocks) if tp_blocks else None
     progress(f"eager blocks {[round(t * 1e3 / args.steps, 3) for t in te_blocks]} ms/step; replayed "
              f"{[round(t * 1e3 / args.steps, 3) for t in tg_blocks]}; profiled {[round(t * 1e3 / args.steps, 3) for t in tp_blocks]}")
     rank_times = rank_blocks[te_blocks.index(elapsed)]
     gal_s = N * world * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
 
     gather_ms, with_gather = None, None
-    if world > 1:
+    if world > 1 and args.full:
         # the optional final collection over xGMI (RCCL all_gather_into_tensor), timed on its own ...
         from gdeconv.dist import gather_batch
         torch.cuda.synchronize()
@@ -620,61 +663,7 @@ def measure(args, ctx):
             if os.path.exists(ipath):
                 os.remove(ipath)
 
-    # live timing: HIP events recorded by the library on each kernel's launch stream and, for whole
-    # operations (op_*), on the caller's stream, over the timed region
-    kernels = {pretty(k): {"avg_ms": ms / c, "launches": c} for k, (ms, c) in kstats.items()}
-    ops = {k: v for k, v in kstats.items() if k.startswith("op_")}
-    kern = {k: v for k, v in kstats.items() if not k.startswith("op_")}
     pipelined = chunk_bytes > 0
-    h_psf = psf.shape[-1]
-    priced_ops = {k: v for k, v in ops.items() if op_bytes(k, L, n, use_fused or pois2 or pois_small, h_psf)}
-    # every priced operation against the HBM spec (compulsory bytes / average call time)
-    for k, (ms, c) in ops.items():
-        b = op_bytes(k, L, n, use_fused or pois2 or pois_small, h_psf)
-        if b:
-            ach = b * N / (ms / c * 1e-3) / 1e9
-            kernels[pretty(k)].update({"algorithmic_bytes_per_call": b * N, "achieved_GBs": ach,
-                                       "frac_of_hbm_peak": ach / HBM_PEAK_GBS})
-    if (pipelined or use_fused or pois2 or pois_small) and priced_ops:
-        # chunks of RF -> C -> RI run concurrently on several streams: the roofline unit is the
-        # whole ADMM iteration (one op_admm_iter call), timed on the caller's stream
-        dom_raw = max(priced_ops, key=lambda k: ops[k][0])
-        dom_ms = ops[dom_raw][0] / ops[dom_raw][1]
-        per_gal = op_bytes(dom_raw, L, n, use_fused or pois2 or pois_small, h_psf)
-    else:
-        priced = {k: v for k, v in kern.items() if kernel_bytes(k, L, n)} or kern
-        dom_raw = max(priced, key=lambda k: kern[k][0])
-        dom_ms = kern[dom_raw][0] / kern[dom_raw][1]
-        per_gal = kernel_bytes(dom_raw, L, n)
-    timing = "HIP events on the caller's stream around each call, the profiled blocks interleaved with value's blocks"
-    if (not rl and dom_ms < 0.05 and pretty(dom_raw) == f"op_admm_iter<{L},{args.llh}>"):
-        # a short op of a host-bound eager forward (48^2): the events also time the host's enqueue gaps, so
-        # the launch duration comes from back-to-back launches replayed as one hipGraph instead
-        dom_ms = graph_iter_ms(obs, psf, alpha, dev, llh=args.llh)
-        timing = "64 back-to-back middle iterations (gd_admm_iter) replayed as one hipGraph, HIP events around it, median of 5 replays"
-    achieved = per_gal * N / (dom_ms * 1e-3) / 1e9 if per_gal else None
-    traffic = None
-    if args.traffic_json is None:
-        suffix = "_rl" if rl else ("_poisson" if args.llh == "Poisson" else "") + ("" if L == 256 else f"_{L}")
-        args.traffic_json = os.path.join(ROOT, "profiles", f"pmc_traffic{suffix}.json")
-    try:
-        with open(args.traffic_json) as f:
-            tj = json.load(f)
-        same_engine = tj.get("engine_rev") == lib.gd_engine_rev().decode()
-        if same_engine and tj.get("batch") == N and tj.get("size") == L and tj.get("n_iters", n) == n:
-            ent = tj.get("kernels", {}).get(pretty(dom_raw))
-            traffic = ent.get("hbm_bytes_per_launch") if ent else None
-            for k, v in kernels.items():  # PMC bytes per call beside every priced operation
-                e = tj.get("kernels", {}).get(k)
-                if e and "algorithmic_bytes_per_call" in v:
-                    v["pmc_traffic_per_call"] = e.get("hbm_bytes_per_launch")
-    except (OSError, ValueError):
-        pass
-    roofline = {"bound": "hbm", "kernel": pretty(dom_raw), "achieved": achieved, "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
-                "traffic": traffic, "algorithmic_bytes_per_launch": per_gal * N if per_gal else None,
-                "avg_launch_ms": dom_ms, "timing": timing}
-    survey_b = survey_rl_bytes_per_galaxy(L, n) if rl else survey_bytes_per_galaxy(L, n)
     if rl:
         metric = f"galaxies/sec ({L}x{L}, Richard_Lucy n_iters={n})"
         workload = (f"Richard_Lucy(n_iters={n}) forward (OTF + {n} multiplicative FFT-conv iterations), "
@@ -728,6 +717,69 @@ def measure(args, ctx):
                              else f"fused, k_pois_small_init ({L}^2: one launch, both images in LDS)"
                              if pois_small and fused_init
                              else "chunked" + (", runtime-planned line FFTs" if generic else "")))},
+    }
+    if not args.full:
+        # a plain run ends here: the headline fields alone
+        if world > 1:
+            rec["ranks"] = {"elapsed_s_min": min(rank_times), "elapsed_s_max": max(rank_times),
+                            "spread": max(rank_times) / min(rank_times) - 1.0, "per_rank_galaxies": N}
+        return rec
+
+    # live timing: HIP events recorded by the library on each kernel's launch stream and, for whole
+    # operations (op_*), on the caller's stream, over the timed region
+    kernels = {pretty(k): {"avg_ms": ms / c, "launches": c} for k, (ms, c) in kstats.items()}
+    ops = {k: v for k, v in kstats.items() if k.startswith("op_")}
+    kern = {k: v for k, v in kstats.items() if not k.startswith("op_")}
+    h_psf = psf.shape[-1]
+    priced_ops = {k: v for k, v in ops.items() if op_bytes(k, L, n, use_fused or pois2 or pois_small, h_psf)}
+    # every priced operation against the HBM spec (compulsory bytes / average call time)
+    for k, (ms, c) in ops.items():
+        b = op_bytes(k, L, n, use_fused or pois2 or pois_small, h_psf)
+        if b:
+            ach = b * N / (ms / c * 1e-3) / 1e9
+            kernels[pretty(k)].update({"algorithmic_bytes_per_call": b * N, "achieved_GBs": ach,
+                                       "frac_of_hbm_peak": ach / HBM_PEAK_GBS})
+    if (pipelined or use_fused or pois2 or pois_small) and priced_ops:
+        # chunks of RF -> C -> RI run concurrently on several streams: the roofline unit is the
+        # whole ADMM iteration (one op_admm_iter call), timed on the caller's stream
+        dom_raw = max(priced_ops, key=lambda k: ops[k][0])
+        dom_ms = ops[dom_raw][0] / ops[dom_raw][1]
+        per_gal = op_bytes(dom_raw, L, n, use_fused or pois2 or pois_small, h_psf)
+    else:
+        priced = {k: v for k, v in kern.items() if kernel_bytes(k, L, n)} or kern
+        dom_raw = max(priced, key=lambda k: kern[k][0])
+        dom_ms = kern[dom_raw][0] / kern[dom_raw][1]
+        per_gal = kernel_bytes(dom_raw, L, n)
+    timing = "HIP events on the caller's stream around each call, the profiled blocks interleaved with value's blocks"
+    if (not rl and dom_ms < 0.05 and pretty(dom_raw) == f"op_admm_iter<{L},{args.llh}>"):
+        # a short op of a host-bound eager forward (48^2): the events also time the host's enqueue gaps, so
+        # the launch duration comes from back-to-back launches replayed as one hipGraph instead
+        dom_ms = graph_iter_ms(obs, psf, alpha, dev, llh=args.llh)
+        timing = "64 back-to-back middle iterations (gd_admm_iter) replayed as one hipGraph, HIP events around it, median of 5 replays"
+    achieved = per_gal * N / (dom_ms * 1e-3) / 1e9 if per_gal else None
+    traffic = None
+    if args.traffic_json is None:
+        suffix = "_rl" if rl else ("_poisson" if args.llh == "Poisson" else "") + ("" if L == 256 else f"_{L}")
+        args.traffic_json = os.path.join(ROOT, "profiles", f"pmc_traffic{suffix}.json")
+    try:
+        with open(args.traffic_json) as f:
+            tj = json.load(f)
+        same_engine = tj.get("engine_rev") == lib.gd_engine_rev().decode()
+        if same_engine and tj.get("batch") == N and tj.get("size") == L and tj.get("n_iters", n) == n:
+            ent = tj.get("kernels", {}).get(pretty(dom_raw))
+            traffic = ent.get("hbm_bytes_per_launch") if ent else None
+            for k, v in kernels.items():  # PMC bytes per call beside every priced operation
+                e = tj.get("kernels", {}).get(k)
+                if e and "algorithmic_bytes_per_call" in v:
+                    v["pmc_traffic_per_call"] = e.get("hbm_bytes_per_launch")
+    except (OSError, ValueError):
+        pass
+    roofline = {"bound": "hbm", "kernel": pretty(dom_raw), "achieved": achieved, "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
+                "traffic": traffic, "algorithmic_bytes_per_launch": per_gal * N if per_gal else None,
+                "avg_launch_ms": dom_ms, "timing": timing}
+    survey_b = survey_rl_bytes_per_galaxy(L, n) if rl else survey_bytes_per_galaxy(L, n)
+    rec.update({
         "roofline": roofline,
         # SURVEY.md 8(d)'s per-galaxy byte model prices the reference's op-for-op path (16 fp32 words per
         # pixel per iteration); this engine's compulsory traffic is 7.5 (roofline above), so the survey
@@ -736,7 +788,7 @@ def measure(args, ctx):
                                "note": "SURVEY 8(d) byte model of the reference's per-iteration FFT round trips; "
                                        "not this engine's traffic (see roofline / kernels.*.algorithmic_bytes_per_call)"},
         "kernels": kernels,
-    }
+    })
     rec["blocks"] = {"eager_ms_per_step": [round(t * 1e3 / args.steps, 4) for t in te_blocks],
                      "graphed_ms_per_step": [round(t * 1e3 / args.steps, 4) for t in tg_blocks],
                      "profiled_ms_per_step": [round(t * 1e3 / args.steps, 4) for t in tp_blocks],

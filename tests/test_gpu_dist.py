@@ -82,7 +82,7 @@ def test_bench_spawns_its_ranks():
     """``bench.py --gpus 2`` with no launcher starts its two ranks itself (gloo rehearsal on one GPU)
     and prints ONE line for the 2-rank job, with the all-gather timings of the multi-rank path."""
     import json
-    r = _bench(["--gpus", "2", "--batch", "64", "--steps", "2", "--warmup", "1", "--no-e2e", "--no-ingest",
+    r = _bench(["--gpus", "2", "--batch", "64", "--steps", "2", "--warmup", "1", "--full", "--no-e2e", "--no-ingest",
                 "--no-cpu-baseline"], {"GD_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -178,28 +178,48 @@ def test_denoiser_micro_batching_is_transparent():
     assert torch.allclose(xg.grad, xf.grad, rtol=0, atol=1e-6 * float(xf.grad.abs().max()))
 
 
-REFERENCE = "/root/reference"
+# A stand-in for the reference checkout, laid out like it (packages ``models`` and ``utils``, each with its own
+# ``__init__.py``): the modules the drop-ins shadow, with the names they leave to the reference, and the
+# modules they do not provide at all.
+_STANDIN_REFERENCE = {
+    "models/__init__.py": "",
+    "models/ADMMNet.py": "class ADMMNet:\n    pass\n",
+    "models/Wiener.py": "class Wiener:\n    reference = True\n",
+    "models/Unrolled_ADMM.py": ("class X_Update:\n    pass\n\n\nclass Z_Update_XDenseUNet:\n    pass\n\n\n"
+                                "class Unrolled_ADMM:\n    reference = True\n"),
+    "utils/__init__.py": "",
+    "utils/fit_ellipse.py": "def fit_ellipse(x, y):\n    return None\n",
+    "utils/utils_test.py": "def delta_2D(gt_shear, rec_shear):\n    return 0.0\n",
+    "utils/utils_train.py": "from utils.fit_ellipse import fit_ellipse  # noqa: F401\n",
+    "utils/utils_torch.py": ("def conv_fft(H, x):\n    return x\n\n\n"
+                             "def conv_fft_batch(H, x):\n    raise AssertionError('the drop-in must win')\n"),
+}
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "models")), reason="reference checkout absent")
-def test_shims_fall_through_to_the_reference():
+def test_shims_fall_through_to_the_reference(tmp_path):
     """With the drop-ins ahead of the reference on sys.path, the
     reference's scripts still import: modules the shims do not provide resolve to the reference's
     files (test.py:15 utils.utils_test, train.py:15 utils.utils_train), names a shim module does not
     define come from the reference module (models.Unrolled_ADMM.X_Update, utils.utils_torch.conv_fft),
-    and the accelerated classes stay the drop-ins.  Runs in a subprocess, bytecode writing off (the
-    reference tree is read-only)."""
+    and the accelerated classes stay the drop-ins.  The reference is a stand-in tree of the same layout
+    written under tmp_path; runs in a subprocess, bytecode writing off."""
     import subprocess
     import sys
+    ref = tmp_path / "reference"
+    for rel, text in _STANDIN_REFERENCE.items():
+        f = ref / rel
+        f.parent.mkdir(parents=True, exist_ok=True)
+        f.write_text(text)
     code = r'''
-import importlib.util, sys
+import importlib.util, os, sys
 sys.dont_write_bytecode = True
+REF = os.path.join(os.environ["GD_TEST_REFERENCE"], "")
 spec = importlib.util.find_spec("utils.utils_test")
-assert spec is not None and spec.origin.startswith("/root/reference/"), spec
+assert spec is not None and spec.origin.startswith(REF), spec
 spec = importlib.util.find_spec("models.ADMMNet")
-assert spec is not None and spec.origin.startswith("/root/reference/"), spec
+assert spec is not None and spec.origin.startswith(REF), spec
 import utils.utils_train as ut                       # imports utils.fit_ellipse from the reference
-assert ut.__file__.startswith("/root/reference/")
+assert ut.__file__.startswith(REF)
 from models.Unrolled_ADMM import Unrolled_ADMM, X_Update, Z_Update_XDenseUNet
 import gdeconv.models
 assert Unrolled_ADMM is gdeconv.models.Unrolled_ADMM
@@ -215,10 +235,9 @@ else:
     raise AssertionError("missing names must still raise")
 print("ok")
 '''
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(repo, "galaxy-deconv_amd"), REFERENCE]),
-               PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", code], env=env, cwd="/tmp", capture_output=True, text=True,
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "galaxy-deconv_amd"), str(ref)]),
+               PYTHONDONTWRITEBYTECODE="1", GD_TEST_REFERENCE=str(ref))
+    r = subprocess.run([sys.executable, "-c", code], env=env, cwd=str(tmp_path), capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
 

@@ -17,7 +17,7 @@ for rd in $(seq 1 $ROUNDS); do
     IFS=';' read -ra CA <<< "$CFGS"
     for cfg in "${CA[@]}"; do
       f=$R/gpurun_out/${OUT}_${rd}_${v}_${i}.json
-      timeout -k 10 240 python3 $R/bench.py $cfg --no-cpu-baseline --no-e2e --no-graph --no-ingest --no-extra > $f 2> $f.err
+      timeout -k 10 240 python3 $R/bench.py $cfg --full --no-cpu-baseline --no-e2e --no-graph --no-ingest --no-extra > $f 2> $f.err
       rc=$?
       if [ $rc -ne 0 ]; then echo "FAIL rc=$rc $v $cfg"; tail -5 $f.err; cp /tmp/ab_orig.so $LIB; exit $rc; fi
       python3 -c "
