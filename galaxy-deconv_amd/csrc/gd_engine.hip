@@ -90,6 +90,8 @@ struct Args {
     int gH, gW;            // image rows / columns (the runtime-size path, gd_generic.hpp)
     int pw;                // PSF columns when the PSF is h x pw, not square (0 = h; the runtime-size path)
     int rev;               // k_gal_reg: workgroup b runs galaxy N - 1 - b (the previous launch's last galaxies first)
+    int tail;              // k_gal_reg (Gaussian): 1 = tail-write (W~ slot <- C, no U1' store), 2 = tail-read (X from C, no U1)
+    GalScalar rho1n;       // tail-write: the last iteration's rho1
 };
 
 enum RowFwdMode { RF_ITER, RF_PSF_Y, RF_PSF_YP, RF_PSF_RAW, RF_PSF, RF_ONE, RF_TWO, RF_YA, RF_PSF_YAR,
@@ -484,16 +486,17 @@ __device__ __forceinline__ GState gauss_load(const Args& a, size_t o) {
 }
 // One bin of the Gaussian iteration (the arithmetic every fused and chunked kernel shares): returns the
 // next denoiser input's bin (X on the last iteration) and the updated U1, W~ (not on the last).
+// r2w: the weight of Wt in X's numerator - rho2, except on a tail-read (below), where the slot holds C and it is 1.
 template <bool LAST>
-__device__ __forceinline__ float2 gauss_math(float hh, float2 Gk, float2 U1, float2 Wt, float2 Zk, float r1, float r2,
-                                             float r2n, float inv_n, float2& U1o, float2& Wo) {
+__device__ __forceinline__ float2 gauss_math_w(float hh, float2 Gk, float2 U1, float2 Wt, float2 Zk, float r1, float r2,
+                                               float r2w, float r2n, float inv_n, float2& U1o, float2& Wo) {
     const float lhs = r1 * hh + r2;
     const float2 A = csub(Zk, U1);
 #if GD_RCP_DIV
     const float rl = __builtin_amdgcn_rcpf(lhs);
-    const float2 X = make_float2((r1 * A.x + r2 * Wt.x) * rl, (r1 * A.y + r2 * Wt.y) * rl);
+    const float2 X = make_float2((r1 * A.x + r2w * Wt.x) * rl, (r1 * A.y + r2w * Wt.y) * rl);
 #else
-    const float2 X = make_float2((r1 * A.x + r2 * Wt.x) / lhs, (r1 * A.y + r2 * Wt.y) / lhs);
+    const float2 X = make_float2((r1 * A.x + r2w * Wt.x) / lhs, (r1 * A.y + r2w * Wt.y) / lhs);
 #endif
     if constexpr (LAST) return cscale(X, inv_n);
     const float2 U1n = csub(cadd(U1, X), Zk);
@@ -510,12 +513,25 @@ __device__ __forceinline__ float2 gauss_math(float hh, float2 Gk, float2 U1, flo
     Wo = csub(Vt, U2t);
     return cscale(cadd(X, U1n), inv_n);
 }
-// gauss_math with the last-iteration choice at run time (uniform per launch): the same operations, in
+template <bool LAST>
+__device__ __forceinline__ float2 gauss_math(float hh, float2 Gk, float2 U1, float2 Wt, float2 Zk, float r1, float r2,
+                                             float r2n, float inv_n, float2& U1o, float2& Wo) {
+    return gauss_math_w<LAST>(hh, Gk, U1, Wt, Zk, r1, r2, r2, r2n, inv_n, U1o, Wo);
+}
+// gauss_math_w with the last-iteration choice at run time (uniform per launch): the same operations, in
 // the same order, as gauss_math<false> / <true>
 __device__ __forceinline__ float2 gauss_math_rt(float hh, float2 Gk, float2 U1, float2 Wt, float2 Zk, float r1,
-                                                float r2, float r2n, float inv_n, float2& U1o, float2& Wo, bool last) {
-    if (last) return gauss_math<true>(hh, Gk, U1, Wt, Zk, r1, r2, r2n, inv_n, U1o, Wo);
-    return gauss_math<false>(hh, Gk, U1, Wt, Zk, r1, r2, r2n, inv_n, U1o, Wo);
+                                                float r2, float r2w, float r2n, float inv_n, float2& U1o, float2& Wo,
+                                                bool last) {
+    if (last) return gauss_math_w<true>(hh, Gk, U1, Wt, Zk, r1, r2, r2w, r2n, inv_n, U1o, Wo);
+    return gauss_math_w<false>(hh, Gk, U1, Wt, Zk, r1, r2, r2w, r2n, inv_n, U1o, Wo);
+}
+// The combined tail.  The last iteration uses U1 and W~ only through C = rho2 W~ - rho1 U1
+// (its own rho1, rho2), so the second-to-last iteration - which holds U1', W~' and the last rho2 (its rho2') -
+// stores C alone in the W~ slot (tail-write, gauss_tail_c; r1n = the last rho1).  The last one (tail-read) is then
+// gauss_math_w<true> with U1 = 0 (not loaded) and r2w = 1: X = (rho1 Z + C) / (rho1 |H|^2 + rho2).
+__device__ __forceinline__ float2 gauss_tail_c(float2 U1n, float2 Wn, float r1n, float r2n) {
+    return make_float2(r2n * Wn.x - r1n * U1n.x, r2n * Wn.y - r1n * U1n.y);
 }
 template <int L, bool FIRST, bool LAST>
 __device__ __forceinline__ float2 gauss_iter_st(const Args& a, size_t o, float2 Zk, const GState& st, float r1,
@@ -2260,7 +2276,10 @@ struct Launcher {
     }
     static int gal_reg(const Args& a, hipStream_t st) {
         ProfScope ps(nm(kGalRegName, a.first + 2 * a.last), st);
-        hipLaunchKernelGGL((k_gal_reg<L>), dim3(a.N), dim3(RegGeo<L>::THREADS), 0, st, a);
+        if (a.tail == 1)
+            hipLaunchKernelGGL((k_gal_reg<L, false, true>), dim3(a.N), dim3(RegGeo<L>::THREADS), 0, st, a);
+        else
+            hipLaunchKernelGGL((k_gal_reg<L>), dim3(a.N), dim3(RegGeo<L>::THREADS), 0, st, a);
         return check_launch("k_gal_reg");
     }
     static int pois_a(const Args& a, hipStream_t st) {
@@ -2326,6 +2345,13 @@ int g_fused_init = 1;  // Gaussian init (256^2: k_psf_rows<STATE> + k_gal_reg_in
 // N < 256 leaves idle (r06j: N = 1 2.1x, 8 2.1x, 32 1.62x, 64 1.28x faster chained; 128 1.17x, 256 1.82x faster fused).
 // The Gaussian state layout is the same either way, so the choice is per call.
 int g_fused_min_n = 96;
+// The combined tail of the 256^2 Gaussian iteration (gauss_math_tail; gd_set_combined_tail).  The default is read
+// from GD_COMBINED_TAIL when the library is loaded (0 = off, anything else or unset = on), so one unchanged program
+// can be measured either way.
+int g_combined_tail = [] {
+    const char* e = std::getenv("GD_COMBINED_TAIL");
+    return (e && e[0] == '0' && e[1] == '\0') ? 0 : 1;
+}();
 // the same for the Poisson two-pass at 256^2 (the state layout follows: 2 from this batch up, 3 below; r06k: the
 // three-kernel chain 3.6x at N = 1, 1.86x at 64, 1.17x at 128 faster, the two-pass 1.25x at 256) and for k_rl_reg
 // (the chunked chain 2.6x at N = 1, 1.46x at 64 faster; k_rl_reg 1.05x at 128, 2.0x at 256)
@@ -2852,7 +2878,7 @@ int gd_abi_version(void) { return GD_ABI_VERSION; }
 
 // bumped whenever a kernel's memory traffic changes; PMC summaries are stamped with it so a stale
 // profile is never reported against a different engine
-const char* gd_engine_rev(void) { return "r06.2"; }
+const char* gd_engine_rev(void) { return "r07.0"; }
 
 // the source hash __graft_entry__.build() computed (gdeconv._lib.source_hash); the "gdsrc:" marker lets the
 // build find it in the binary without loading it
@@ -3022,12 +3048,28 @@ int gd_admm_init(const float* y, const float* psf, long long psf_gstride, int h,
     return dispatch<Ops>(H, W, [&](auto op) { return decltype(op)::admm_init(a, (hipStream_t)stream); });
 }
 
-int gd_admm_iter(const float* y, const float* z, float* zin_or_out, const float* alpha, long long alpha_stride,
-                 const float* rho1, long long rho1_stride, const float* rho2, long long rho2_stride,
-                 const float* rho2_next, long long rho2_next_stride, int llh, int iter, int last, int N, int H,
-                 int W, void* state, void* ws, void* stream) {
+// 1 exactly when gd_admm_iter would run k_gal_reg now (admm_iter_gauss's first branch) and the switch is on
+int gd_admm_tail_supported(int N, int H, int W, int llh) {
+    return llh == GD_LLH_GAUSSIAN && H == 256 && W == 256 && has_fused<256>() && g_fused != 0 && N >= g_fused_min_n &&
+                   g_combined_tail != 0
+               ? 1
+               : 0;
+}
+
+int gd_admm_iter_tail(const float* y, const float* z, float* zin_or_out, const float* alpha, long long alpha_stride,
+                      const float* rho1, long long rho1_stride, const float* rho2, long long rho2_stride,
+                      const float* rho2_next, long long rho2_next_stride, int llh, int iter, int last, int N, int H,
+                      int W, void* state, void* ws, void* stream, const float* rho1_next, long long rho1_next_stride,
+                      int tail) {
     GD_TRY(check_shape(N, H, W));
     if (llh != GD_LLH_GAUSSIAN && llh != GD_LLH_POISSON) return fail(GD_ERR_ARG, "llh must be Gaussian or Poisson");
+    if (tail < 0 || tail > 2) return fail(GD_ERR_ARG, "tail must be 0, 1 (tail-write) or 2 (tail-read)");
+    if (tail == 1 && last) return fail(GD_ERR_ARG, "tail = 1 (the next call is the last) with last set");
+    if (tail == 1 && rho1_next == nullptr) return fail(GD_ERR_ARG, "tail = 1 needs rho1_next (the last iteration's rho1)");
+    if (tail == 2 && !last) return fail(GD_ERR_ARG, "tail = 2 (the W~ slot holds the combined term) is the last call only");
+    if (tail == 2 && iter == 0) return fail(GD_ERR_ARG, "tail = 2 follows a tail = 1 call: it cannot be iteration 0");
+    if (tail != 0 && !gd_admm_tail_supported(N, H, W, llh))
+        return fail(GD_ERR_UNSUPPORTED, "no combined tail on the path this call routes to (gd_admm_tail_supported)");
     if (N == 0) return GD_OK;
     if (!last && rho2_next == nullptr) return fail(GD_ERR_ARG, "rho2_next required unless last");
     Args a = base_args(N, ws, H, W);
@@ -3037,6 +3079,8 @@ int gd_admm_iter(const float* y, const float* z, float* zin_or_out, const float*
     a.rho1 = GalScalar{rho1, rho1_stride};
     a.rho2 = GalScalar{rho2, rho2_stride};
     a.rho2n = GalScalar{rho2_next ? rho2_next : rho2, rho2_next ? rho2_next_stride : rho2_stride};
+    a.tail = tail;
+    if (tail == 1) a.rho1n = GalScalar{rho1_next, rho1_next_stride};
     a.llh = llh;
     a.last = last;
     a.first = iter == 0;
@@ -3059,6 +3103,24 @@ int gd_admm_iter(const float* y, const float* z, float* zin_or_out, const float*
     a.a0 = z; a.a1 = a.o0; a.a2 = a.o1;
     a.o2 = zin_or_out;
     return dispatch<Ops>(H, W, [&](auto op) { return decltype(op)::admm_iter(a, (hipStream_t)stream); });
+}
+
+int gd_admm_iter(const float* y, const float* z, float* zin_or_out, const float* alpha, long long alpha_stride,
+                 const float* rho1, long long rho1_stride, const float* rho2, long long rho2_stride,
+                 const float* rho2_next, long long rho2_next_stride, int llh, int iter, int last, int N, int H,
+                 int W, void* state, void* ws, void* stream) {
+    return gd_admm_iter_tail(y, z, zin_or_out, alpha, alpha_stride, rho1, rho1_stride, rho2, rho2_stride, rho2_next,
+                             rho2_next_stride, llh, iter, last, N, H, W, state, ws, stream, nullptr, 0, 0);
+}
+
+int gd_admm_iter_tail_v(const long long* v) {
+    if (v == nullptr) return fail(GD_ERR_ARG, "gd_admm_iter_tail_v: null argument vector");
+    const auto p = [v](int i) { return reinterpret_cast<void*>(static_cast<intptr_t>(v[i])); };
+    return gd_admm_iter_tail(static_cast<const float*>(p(0)), static_cast<const float*>(p(1)), static_cast<float*>(p(2)),
+                             static_cast<const float*>(p(3)), v[4], static_cast<const float*>(p(5)), v[6],
+                             static_cast<const float*>(p(7)), v[8], static_cast<const float*>(p(9)), v[10], (int)v[11],
+                             (int)v[12], (int)v[13], (int)v[14], (int)v[15], (int)v[16], p(17), p(18), p(19),
+                             static_cast<const float*>(p(20)), v[21], (int)v[22]);
 }
 
 int gd_admm_iter_v(const long long* v) {
@@ -3292,6 +3354,13 @@ int gd_set_fused_min_batch(int op, int n) {
 int gd_set_subnet_fused_max(int n) {
     const int old = g_subnet_fused_max;
     if (n >= 0) g_subnet_fused_max = n;
+    return old;
+}
+
+int gd_set_combined_tail(int on) {
+    if (on != 0 && on != 1) return fail(GD_ERR_ARG, "gd_set_combined_tail: 0 or 1");
+    const int old = g_combined_tail;
+    g_combined_tail = on;
     return old;
 }
 

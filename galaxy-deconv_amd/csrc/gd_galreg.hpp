@@ -73,7 +73,7 @@ __device__ __forceinline__ float2 pois_math(float2 Hk, float2 U1, float2 Wf, flo
 // the Nyquist column, one bin per thread (ky = tid)
 template <int L, bool POIS = false>
 __device__ __forceinline__ float2 gauss_bin4(const Args& a, int g, int ky, float2 Zk, float r1, float r2, float r2n,
-                                             bool first, bool last) {
+                                             bool first, bool last, float r2w, bool tread, bool twrite, float r1n) {
     constexpr float inv_n = float(1.0 / double(L * L));
     const size_t cb = ((size_t)g * (L / 2 + 1) + L / 2) * L;
     const int pc = sidx_c<L>(ky);
@@ -89,13 +89,14 @@ __device__ __forceinline__ float2 gauss_bin4(const Args& a, int g, int ky, float
     }
     const float hh = a.s_hh[cb + sidx_h<L>(ky)];
     const float2 Gk = (last && !first) ? make_float2(0.f, 0.f) : a.s_g[cb + pc];
-    const float2 U1 = first ? make_float2(0.f, 0.f) : a.s_u1[cb + pc];
+    const float2 U1 = (first || tread) ? make_float2(0.f, 0.f) : a.s_u1[cb + pc];  // tail-read: C needs no U1
     float2 Wt = a.s_w[cb + pc];
     if (first) Wt = w1_value(hh, Gk, Wt, r2);  // the slot holds F(x0) (w1_value)
     float2 U1n, Wn;
-    const float2 r = gauss_math_rt(hh, Gk, U1, Wt, Zk, r1, r2, r2n, inv_n, U1n, Wn, last);
+    const float2 r = gauss_math_rt(hh, Gk, U1, Wt, Zk, r1, r2, r2w, r2n, inv_n, U1n, Wn, last);
     if (!last) {
-        st_s(a.s_u1 + cb + pc, U1n);
+        if (twrite) Wn = gauss_tail_c(U1n, Wn, r1n, r2n);  // tail-write: C alone, in the W~ slot
+        else st_s(a.s_u1 + cb + pc, U1n);
         st_s(a.s_w + cb + pc, Wn);
     }
     return r;
@@ -115,14 +116,15 @@ struct SGroup {
 };
 template <int L, bool POIS = false>
 __device__ __forceinline__ void sgroup_load(const Args& a, SGroup& G, size_t gb, int kx, int q, int j, bool first,
-                                            bool last) {
+                                            bool last, bool tread) {
     G.h = POIS ? f4v{0.f, 0.f, 0.f, 0.f} : ld4s(a.s_hh + gb + soff_h(kx, q, j));  // Poisson: |H|^2 from H
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const size_t off = gb + soff_c(kx, 2 * q + h, j);
         // Gaussian G (first: W~1 needs it; not on the last); Poisson: the OTF H (the G slot)
         G.g[h] = (!POIS && last && !first) ? f4v{0.f, 0.f, 0.f, 0.f} : ld4s(a.s_g + off);
-        G.u[h] = first ? f4v{0.f, 0.f, 0.f, 0.f} : ld4s(a.s_u1 + off);
+        // (Gaussian tail-read: |H|^2 and the W~ slot, which holds C, only)
+        G.u[h] = (first || tread) ? f4v{0.f, 0.f, 0.f, 0.f} : ld4s(a.s_u1 + off);
         G.w[h] = ld4s(a.s_w + off);
     }
 }
@@ -143,17 +145,18 @@ __device__ __forceinline__ void sgroup_load(const Args& a, SGroup& G, size_t gb,
 #endif
 template <int L, int NC, bool POIS = false, int D = GD_REG_DEPTH>
 __device__ __forceinline__ void fused_prefetch4x(const Args& a, SGroup (&P)[D], int g, int kx0, int kstep, int j, bool first,
-                                                 bool last) {
+                                                 bool last, bool tread) {
     j = opaque(j);
     kx0 = opaque(kx0);
     const size_t gb = (size_t)g * (L / 2 + 1) * L;
 #pragma unroll
-    for (int t = 0; t < D && t < 4 * NC; ++t) sgroup_load<L, POIS>(a, P[t], gb, kx0 + kstep * (t / 4), t % 4, j, first, last);
+    for (int t = 0; t < D && t < 4 * NC; ++t) sgroup_load<L, POIS>(a, P[t], gb, kx0 + kstep * (t / 4), t % 4, j, first, last, tread);
     __builtin_amdgcn_sched_barrier(0);
 }
-template <int L, int NC, bool POIS = false, int D = GD_REG_DEPTH, bool PRE = false>
+template <int L, int NC, bool POIS = false, int D = GD_REG_DEPTH, bool PRE = false, bool TWRITE = false>
 __device__ __forceinline__ void fused_update4x(const Args& a, float2 (&C)[NC][16], int g, int kx0, int kstep, int j,
-                                               float r1, float r2, float r2n, bool first, bool last,
+                                               float r1, float r2, float r2n, bool first, bool last, float r2w, bool tread,
+                                               float r1n,
                                                const SGroup (*pre)[D] = nullptr) {
     constexpr float inv_n = float(1.0 / double(L * L));
     constexpr int NG = 4 * NC;
@@ -165,7 +168,7 @@ __device__ __forceinline__ void fused_update4x(const Args& a, float2 (&C)[NC][16
 #pragma unroll
     for (int t = 0; t < D && t < NG; ++t) {
         if constexpr (PRE) G[t] = (*pre)[t];
-        else sgroup_load<L, POIS>(a, G[t], gb, kx0 + kstep * (t / 4), t % 4, j, first, last);
+        else sgroup_load<L, POIS>(a, G[t], gb, kx0 + kstep * (t / 4), t % 4, j, first, last, tread);
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -184,7 +187,8 @@ __device__ __forceinline__ void fused_update4x(const Args& a, float2 (&C)[NC][16
             } else {
                 if (first) Wt = w1_value(G[t].h[e], Gk, Wt, r2);  // the slot holds F(x0) (w1_value)
                 C[u][4 * q + e] = gauss_math_rt(G[t].h[e], Gk, make_float2(G[t].u[h][c], G[t].u[h][c + 1]), Wt,
-                                                C[u][4 * q + e], r1, r2, r2n, inv_n, U1n, Wn, last);
+                                                C[u][4 * q + e], r1, r2, r2w, r2n, inv_n, U1n, Wn, last);
+                if constexpr (TWRITE) Wn = gauss_tail_c(U1n, Wn, r1n, r2n);
             }
             uo[h][c] = U1n.x; uo[h][c + 1] = U1n.y;
             wo[h][c] = Wn.x; wo[h][c + 1] = Wn.y;
@@ -193,11 +197,11 @@ __device__ __forceinline__ void fused_update4x(const Args& a, float2 (&C)[NC][16
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const size_t off = gb + soff_c(kx0 + kstep * u, 2 * q + h, j);
-                st4v(a.s_u1 + off, uo[h]);
+                if constexpr (!TWRITE) st4v(a.s_u1 + off, uo[h]);  // tail-write: C alone, in the W~ slot
                 st4v((POIS ? a.s_x : a.s_w) + off, wo[h]);
             }
         }
-        if (t + D < NG) sgroup_load<L, POIS>(a, G[t + D], gb, kx0 + kstep * ((t + D) / 4), (t + D) % 4, j, first, last);
+        if (t + D < NG) sgroup_load<L, POIS>(a, G[t + D], gb, kx0 + kstep * ((t + D) / 4), (t + D) % 4, j, first, last, tread);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -278,8 +282,16 @@ __device__ __forceinline__ void stagger_start(int g, int N) {
 // code's register allocation is spill-free, compile-time FIRST / LAST variants spilled 60-100 VGPRs.
 // POIS: Poisson pass A (k_gal_reg<L, true>): the same skeleton with pois_math's update (no V step, no G;
 // U1', X out) and the last output x * alpha (models/Unrolled_ADMM.py:215)
-template <int L, bool POIS = false>
+// The combined tail (gd_engine.hip: gauss_tail_c; Args::tail, uniform per launch).  Tail-READ (tail = 2, a last
+// iteration) is a run-time mode like first / last: it only turns U1's loads off and sets the W~ slot's weight in
+// X's numerator to 1 (r2w), outside the update loop.  Tail-WRITE is the compile-time variant TWRITE (picked by the
+// launcher): as a run-time flag inside the update loop it broke up the packed bin math of EVERY launch (k_gal_reg
+// 10978 -> 12625 instructions, scalar FMAs in place of packed ones), while this variant only adds 4 FMAs per bin
+// and drops a store (232 VGPRs like the plain kernel; a compile-time tail-read variant spilled 84).
+// Gaussian only: Poisson pass A, whose registers are full, compiles none of it.
+template <int L, bool POIS = false, bool TWRITE = false>
 __global__ __launch_bounds__(512) void k_gal_reg(Args a) {
+    static_assert(!POIS || !TWRITE, "the combined tail is Gaussian only");
     using RG = RegGeo<L>;
     constexpr int F1 = RG::F1, F2 = RG::F2, KS = RG::KS, SLD = RG::SLD, LINES = RG::LINES, T = RG::THREADS;
     constexpr int RB0 = RG::RB0, RB1 = RG::RB1;
@@ -298,6 +310,11 @@ __global__ __launch_bounds__(512) void k_gal_reg(Args a) {
     const float r1 = a.rho1(g), r2 = a.rho2(g);
     const bool first = __builtin_amdgcn_readfirstlane(a.first) != 0, last = __builtin_amdgcn_readfirstlane(a.last) != 0;
     const float r2n = (POIS || last) ? 0.f : a.rho2n(g);
+    bool tread = false;
+    float r1n = 0.f;
+    if constexpr (TWRITE) r1n = a.rho1n(g);
+    else if constexpr (!POIS) tread = __builtin_amdgcn_readfirstlane(a.tail) == 2;
+    const float r2w = tread ? 1.f : r2;
     const float al = POIS ? a.alpha(g) : 1.f;
     GD_TRACE(0);
 
@@ -362,7 +379,7 @@ __global__ __launch_bounds__(512) void k_gal_reg(Args a) {
     constexpr int DPT = POIS ? GD_POIS_DEPTH : GD_REG_DEPTH;
     constexpr bool SPF = GD_REG_SPF && (!POIS || GD_POIS_SPF);
     SGroup preA[DPT];
-    if constexpr (SPF) fused_prefetch4x<L, RG::CPL, POIS, DPT>(a, preA, g, line, LINES, j, first, last);
+    if constexpr (SPF) fused_prefetch4x<L, RG::CPL, POIS, DPT>(a, preA, g, line, LINES, j, first, last, tread);
     if constexpr ((GD_REG_PAIR & 1) != 0 && (!POIS || GD_POIS_PAIR)) {
         reg_fft2<L, false>(CA[0], CA[1], opaque(j), my, tw);
         __builtin_amdgcn_sched_barrier(0);
@@ -387,9 +404,9 @@ __global__ __launch_bounds__(512) void k_gal_reg(Args a) {
     }
     lds_barrier();  // nyqc complete
     if (__builtin_amdgcn_readfirstlane(tid >> 6) < L / 64) {
-        nyqc[tid] = gauss_bin4<L, POIS>(a, g, tid, nyqc[tid], r1, r2, r2n, first, last);
+        nyqc[tid] = gauss_bin4<L, POIS>(a, g, tid, nyqc[tid], r1, r2, r2n, first, last, r2w, tread, TWRITE, r1n);
     }
-    fused_update4x<L, RG::CPL, POIS, DPT, SPF>(a, CA, g, line, LINES, j, r1, r2, r2n, first, last, &preA);
+    fused_update4x<L, RG::CPL, POIS, DPT, SPF, TWRITE>(a, CA, g, line, LINES, j, r1, r2, r2n, first, last, r2w, tread, r1n, &preA);
     lds_barrier();  // Nyquist results
     GD_TRACE(4);
 #pragma unroll
@@ -444,7 +461,7 @@ __global__ __launch_bounds__(512) void k_gal_reg(Args a) {
     __builtin_amdgcn_sched_barrier(0);
     GD_TRACE(6);
     SGroup preB[DPT];
-    if constexpr (SPF) fused_prefetch4x<L, RG::CPL, POIS, DPT>(a, preB, g, KS + line, LINES, j, first, last);
+    if constexpr (SPF) fused_prefetch4x<L, RG::CPL, POIS, DPT>(a, preB, g, KS + line, LINES, j, first, last, tread);
     if constexpr ((GD_REG_PAIR & 1) != 0 && (!POIS || GD_POIS_PAIR)) {
         reg_fft2<L, false>(CB[0], CB[1], opaque(j), my, tw);
         __builtin_amdgcn_sched_barrier(0);
@@ -455,7 +472,7 @@ __global__ __launch_bounds__(512) void k_gal_reg(Args a) {
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    fused_update4x<L, RG::CPL, POIS, DPT, SPF>(a, CB, g, KS + line, LINES, j, r1, r2, r2n, first, last, &preB);
+    fused_update4x<L, RG::CPL, POIS, DPT, SPF, TWRITE>(a, CB, g, KS + line, LINES, j, r1, r2, r2n, first, last, r2w, tread, r1n, &preB);
     if constexpr ((GD_REG_PAIR & 2) != 0 && (!POIS || GD_POIS_PAIR)) {
         reg_fft2<L, true>(CB[0], CB[1], opaque(j), my, tw);
         __builtin_amdgcn_sched_barrier(0);

@@ -587,6 +587,7 @@ class ADMMState:
         self._bind()
         self.layout = None
         self.iter = 0
+        self._tail = False  # the last step was a tail-write: the W~ slot holds C, good for exactly one last step
         self._side = None   # the _side_streams entry an init_concurrent() is running on, until joined
         # not cached: for Poisson it follows the fused-path switches (state layout 4: iteration 0 forms w1);
         # _reads_rho holds overrides only (tests force the serial order with it)
@@ -630,6 +631,7 @@ class ADMMState:
                 self.W, sp, self.zin.data_ptr(), wp, _stream(self.dev)), "gd_admm_init")
         self.layout = self.lib.gd_admm_state_layout(self.N, self.H, self.W, self.llh)
         self.iter = 0
+        self._tail = False
 
     def init_with_subnet(self, params, mlp_params, n_out):
         """``init`` and the engine SubNet (``subnet_rhos_psf`` of this state's PSFs and alphas; packs from
@@ -656,6 +658,7 @@ class ADMMState:
                 rhos.data_ptr(), int(n_out), wp, _stream(self.dev)), "gd_admm_init_subnet")
         self.layout = self.lib.gd_admm_state_layout(self.N, self.H, self.W, self.llh)
         self.iter = 0
+        self._tail = False
         return rhos
 
     def init_concurrent(self):
@@ -703,21 +706,27 @@ class ADMMState:
             self._side = None
 
     def _bind(self):
-        """The packed argument vector of gd_admm_iter_v (its 20 slots in gd_admm_iter's order): the slots fixed for
+        """The packed argument vector of gd_admm_iter_tail_v (its 23 slots: gd_admm_iter's 20 in order, then rho1_next,
+        its stride and ``tail``): the slots fixed for
         this state (y, alpha, llh, N, H, W, state, workspace) set here from ``_fixed``, the per-call ones by ``step``
         (one 1-argument ctypes call per iteration instead of 20 converted arguments: the eager 256 x 48^2 forward is
         host-bound).  Call again after re-pointing ``_fixed``."""
         yp, ap, as_, sp, wp = self._fixed
-        v = self._argv = (ctypes.c_longlong * 20)()
+        v = self._argv = (ctypes.c_longlong * 23)()
         v[0], v[3], v[4], v[11] = yp, ap, as_, self.llh
         v[14], v[15], v[16], v[17], v[18] = self.N, self.H, self.W, sp, wp
         self._argv_addr = ctypes.addressof(v)
-        self._iter_v = self.lib.gd_admm_iter_v
+        self._iter_v = self.lib.gd_admm_iter_tail_v
 
-    def step(self, z, rho1, rho2, rho2_next, out=None):
+    def step(self, z, rho1, rho2, rho2_next, out=None, *, rho1_next=None):
         """One loop body (models/Unrolled_ADMM.py:207-213) after the denoiser returned ``z``.
         ``rho*`` are (tensor or device pointer, stride) pairs (``RhoSchedule`` items); ``rho2_next`` None
-        marks the last iteration, whose x (times alpha for Poisson) goes to ``out``."""
+        marks the last iteration, whose x (times alpha for Poisson) goes to ``out``.
+
+        ``rho1_next``: given on the second-to-last iteration (the next step's rho1), it lets the 256^2 Gaussian
+        whole-galaxy kernel store the one combination of U1' and W~' the last iteration needs instead of both
+        (gd_admm_iter_tail).  The state is then good for exactly one more step, the last one:
+        any other step raises, as does a last step after the routing switches changed."""
         if self.layout is None:
             raise _lib.EngineError("ADMMState.step before init")
         if self._side is not None:
@@ -740,6 +749,20 @@ class ADMMState:
             raise _lib.EngineError("the ADMM state layout changed since init (gd_set_fused_iteration toggled "
                                    "between gd_admm_init and gd_admm_iter)")
         v = self._argv
+        tail = 0
+        if self._tail:
+            if not last:
+                raise _lib.EngineError("the previous step was a tail-write (rho1_next given): the state holds the "
+                                       "last iteration's combined term only, the next step must be the last")
+            tail = 2   # (a routing switch toggled since the tail-write: GD_ERR_UNSUPPORTED below)
+        elif rho1_next is not None and not last and self.llh == 0 and self.H == 256 and self.W == 256 \
+                and self.lib.gd_admm_tail_supported(self.N, self.H, self.W, self.llh) == 1:
+            tail = 1   # one query per forward, and only where a tail exists
+        if tail == 1:
+            v[20], v[21] = _scalar_arg(rho1_next, self.dev)
+        else:
+            v[20], v[21] = 0, 0
+        v[22] = tail
         v[5], v[6] = _scalar_arg(rho1, self.dev)
         v[7], v[8] = _scalar_arg(rho2, self.dev)
         if last:
@@ -756,6 +779,7 @@ class ADMMState:
                 rc = self._iter_v(self._argv_addr)
         if rc:
             _lib.check(rc, "gd_admm_iter")
+        self._tail = tail == 1
         self.iter += 1
         return dst
 

@@ -128,7 +128,9 @@ class Unrolled_ADMM(nn.Module):
         out = torch.empty_like(st.y)
         for it in range(n):
             z = self.Z(st.zin)
-            st.step(z, r1[it], r2[it], r2[it + 1] if it + 1 < n else None, out=out)
+            # iteration n - 2 may fold the duals it leaves into the one term the last iteration reads (rho1_next)
+            st.step(z, r1[it], r2[it], r2[it + 1] if it + 1 < n else None, out=out,
+                    rho1_next=r1[it + 1] if it == n - 2 else None)
         return out
 
 

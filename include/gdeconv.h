@@ -24,6 +24,7 @@
  *   gd_admm_init        models/Unrolled_ADMM.py:181-196 + init_l2 :170-175 (+ first V step of :207)
  *   gd_admm_iter        models/Unrolled_ADMM.py:199-214 loop body around the denoiser call :208
  *   gd_admm_iter_v      the same, arguments packed (interpreted callers)
+ *   gd_admm_iter_tail   the same, with the last two iterations' duals folded into one spectrum (256^2 Gaussian)
  *                       (X_Update :315-319, V_Update_{Poisson,Gaussian} :326-328/:335-336, duals
  *                       :212-213, next V step, output scaling :215)
  *   gd_wiener           models/Wiener.py:10-20       Wiener.forward(y, psf, alpha)
@@ -130,6 +131,33 @@ int gd_admm_iter(const float* y, const float* z, float* zin_or_out, const float*
  * per-argument conversion costs more than the call (Python ctypes: 2.9 us for the 20-argument call, 0.6 us for a
  * short one) - at 256 x 48^2 the host sets the pace of an eager forward (gdeconv.engine.ADMMState.step). */
 int gd_admm_iter_v(const long long* argv);
+
+/* The combined tail of the Gaussian iteration at 256^2 (k_gal_reg).  The last iteration uses the duals only through
+ * C = rho2 W~ - rho1 U1 with its own rho1, rho2: x = (rho1 Z + C) / (rho1 |H|^2 + rho2).  gd_admm_iter_tail is
+ * gd_admm_iter plus rho1_next (the NEXT call's rho1, per galaxy like the other rhos) and `tail`:
+ *   0  gd_admm_iter exactly (rho1_next ignored).
+ *   1  the next call is the last one: this call stores C (formed with rho1_next and rho2_next) in the state's W~
+ *      slot and does NOT store U1' - one half spectrum less written.  GD_ERR_ARG if last != 0 or rho1_next is NULL.
+ *   2  last != 0 and the previous call was a tail = 1 call: x is formed from |H|^2 and C alone, U1 and G are not
+ *      read - one half spectrum less read.  GD_ERR_ARG if last == 0 or iter == 0.
+ * CONTRACT: after a tail = 1 call the state is good for exactly one more call, the last one with tail = 2, with the
+ * rho1 / rho2 that were this call's rho1_next / rho2_next.  A tail = 0 call on such a state would read C as W~ and a
+ * stale U1; the engine cannot detect that (gdeconv.engine.ADMMState does, for its own callers).  zin_or_out of the
+ * tail = 1 call is the usual next denoiser input; results agree with the tail = 0 pair to rounding (C is rounded
+ * once where U1' and W~' were rounded separately), not bit for bit.
+ * tail != 0 where the call would not run k_gal_reg (gd_admm_tail_supported below) is GD_ERR_UNSUPPORTED - also for a
+ * tail = 2 call after a routing switch was toggled: it fails rather than compute from a mis-read slot.  All
+ * validation precedes any HIP call. */
+int gd_admm_iter_tail(const float* y, const float* z, float* zin_or_out, const float* alpha, long long alpha_stride,
+                      const float* rho1, long long rho1_stride, const float* rho2, long long rho2_stride,
+                      const float* rho2_next, long long rho2_next_stride, int llh, int iter, int last, int N, int H,
+                      int W, void* state, void* ws, void* stream, const float* rho1_next, long long rho1_next_stride,
+                      int tail);
+/* gd_admm_iter_tail with its 23 arguments packed in that order (as gd_admm_iter_v packs gd_admm_iter's 20). */
+int gd_admm_iter_tail_v(const long long* argv);
+/* 1 exactly when gd_admm_iter would run k_gal_reg NOW for this call (Gaussian, 256^2, gd_set_fused_iteration on,
+ * N >= gd_set_fused_min_batch(0, .)) and gd_set_combined_tail is on; else 0. */
+int gd_admm_tail_supported(int N, int H, int W, int llh);
 
 /* x = Re IFFT2(conj(H) FFT2(y) / (|H|^2 + 350/alpha)). */
 int gd_wiener(const float* y, const float* psf, long long psf_gstride, int h, int w, const float* alpha,
@@ -246,6 +274,12 @@ int gd_set_capture_pipeline(int mode);
  * the workspace).  Returns the previous setting (0 or 1), or GD_ERR_ARG (setting unchanged) for any other value;
  * process-wide. */
 int gd_set_fused_iteration(int on);
+
+/* The combined tail (gd_admm_iter_tail): on = 1 lets gd_admm_tail_supported answer 1, 0 makes it answer 0 everywhere
+ * (callers then issue plain iterations).  The default is 1, or 0 when the environment variable GD_COMBINED_TAIL is
+ * "0" at load.  Returns the previous setting (0 or 1), or GD_ERR_ARG (setting unchanged) for any other value;
+ * process-wide. */
+int gd_set_combined_tail(int on);
 
 /* Richardson-Lucy at 256^2 (gd_richardson_lucy, models/Richard_Lucy.py:10-24): on = 1 (default) runs the
  * OTF, then the whole n_iters loop of each galaxy inside one 512-thread workgroup (k_rl_reg: the

@@ -7,6 +7,7 @@ int main(int argc, char**) {
     if (argc > 1000) {  // never true: instantiation only
         gd::Args a{};
         hipLaunchKernelGGL((gd::k_gal_reg<256, false>), dim3(1), dim3(512), 0, 0, a);
+        hipLaunchKernelGGL((gd::k_gal_reg<256, false, true>), dim3(1), dim3(512), 0, 0, a);  // tail-write
         hipLaunchKernelGGL((gd::k_gal_reg<256, true>), dim3(1), dim3(512), 0, 0, a);
         hipLaunchKernelGGL((gd::k_gal_reg_init<256, false>), dim3(1), dim3(512), 0, 0, a);
         hipLaunchKernelGGL((gd::k_gal_reg_init<256, true>), dim3(1), dim3(512), 0, 0, a);

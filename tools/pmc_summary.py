@@ -60,7 +60,7 @@ def pretty(kname):
     m = re.search(r"k_rl_reg<(\d+)>", kname)
     if m:
         return f"k_rl_reg<{m.group(1)}>"              # whole Richardson-Lucy loop per galaxy
-    m = re.search(r"k_gal_reg<(\d+)(?:, (true|false))?>", kname)
+    m = re.search(r"k_gal_reg<(\d+)(?:, (true|false))?(?:, (?:true|false))?>", kname)  # (third: the tail-write variant)
     if m:
         if m.group(2) == "true":
             return f"k_pois_a<{m.group(1)}>"          # Poisson pass A
