@@ -22,6 +22,8 @@
 //   conv_fft_batch      utils/utils_torch.py:46-50      -> RF_ONE, C_CONV[C], RI_OUT1
 //   init_l2             models/Unrolled_ADMM.py:170-175 -> RF_PSF_Y, C_OTF_INIT, RIF_CLAMP, C_CONV, RI_INIT
 //   ADMM loop body      models/Unrolled_ADMM.py:199-214 -> RF_ITER, C_ITER, RI_ITER
+//   the same, for training (out of place, saving conj(H) W - X and vt) -> RF_ITER, C_TRAIN, RI_TRAIN
+//   its adjoint (gd_admm_train_iter_backward)           -> RF_TRAIN_BWD, C_TRAIN_BWD, RI_TRAIN_BWD
 //   Wiener.forward      models/Wiener.py:10-20          -> RF_PSF_RAW, C_WIENER, RI_OUT1
 //   Richard_Lucy.forward models/Richard_Lucy.py:10-24   -> RF_PSF_YP, C_OTF_CONV, RIF_RL_RATIO,
 //                                                          C_CONVC, RIF_RL_UPDATE / RI_RL_FINAL, C_CONV
@@ -92,14 +94,20 @@ struct Args {
     int rev;               // k_gal_reg: workgroup b runs galaxy N - 1 - b (the previous launch's last galaxies first)
     int tail;              // k_gal_reg (Gaussian): 1 = tail-write (W~ slot <- C, no U1' store), 2 = tail-read (X from C, no U1)
     GalScalar rho1n;       // tail-write: the last iteration's rho1
+    const float* a3;       // training body (gd_admm_train_*): the saved vt image (backward input)
+    float* o3;             //   the vt image the forward saves
+    float* part;           //   backward: d loss / d rho parts [N][2 K + H] (rho1 | rho2 per kx, rho2_next per row)
 };
 
 enum RowFwdMode { RF_ITER, RF_PSF_Y, RF_PSF_YP, RF_PSF_RAW, RF_PSF, RF_ONE, RF_TWO, RF_YA, RF_PSF_YAR,
-                  RF_PADV, RF_PSF_YPAD, RF_PAD2 };  // RF_PAD*: L/2 x L/2 sources zero-padded to L x L
+                  RF_PADV, RF_PSF_YPAD, RF_PAD2,    // RF_PAD*: L/2 x L/2 sources zero-padded to L x L
+                  RF_TRAIN_BWD };                   // adjoint of the training body: g_x, g_hx from the incoming gradients
 enum ColMode { C_ITER, C_OTF_INIT, C_OTF_CONV, C_WIENER, C_OTF, C_CONV, C_CONVC, C_CONV2, C_FWD, C_INV,
                C_G_INIT, C_G_ITER, C_G_W1, C_G_ITER_F, C_G_ITER_L, C_G_ITER_FL,  // _F first, _L last iteration
-               C_TIKHONOV, C_POWER, C_GX_INIT, C_GX, C_GX_BWD };
-enum RowInvMode { RI_ITER, RI_INIT, RI_OUT1, RI_OUT2, RI_RL_FINAL, RI_CROP, RI_CROP_BWD };  // RI_CROP*: L/2 x L/2 sinks
+               C_TIKHONOV, C_POWER, C_GX_INIT, C_GX, C_GX_BWD,
+               C_TRAIN, C_TRAIN_BWD };  // C_ITER that saves conj(H) W - X for the backward; its adjoint
+enum RowInvMode { RI_ITER, RI_INIT, RI_OUT1, RI_OUT2, RI_RL_FINAL, RI_CROP, RI_CROP_BWD,  // RI_CROP*: L/2 x L/2 sinks
+                  RI_TRAIN, RI_TRAIN_BWD };  // RI_ITER out of place (saves vt); the adjoint's sink
 enum RowInvFwdMode { RIF_CLAMP, RIF_RL_RATIO, RIF_RL_UPDATE };
 
 constexpr int rows_per_block(int lpb, int L) {
@@ -141,6 +149,26 @@ __device__ __forceinline__ float v_step(int llh, float vt, float yp, float rho2,
         return 0.5f * (1.0f / rho2) * (-t1 + sqrtf(t1 * t1 + 4.0f * yp * rho2));
     }
     return (rho2 * vt + yp / alpha) / (1.0f + rho2);
+}
+
+// d V / d vt and d V / d rho2 of the V step at (vt, yp, rho2, alpha): the local factors of the training backward
+// (gd_admm_train_iter_backward).  Poisson: with s = sqrt(t^2 + 4 yp rho2), s - t is formed as 4 yp rho2 / (s + t) where
+// t > 0 (no cancellation); yp = 0 and t = 0 give s = 0 and a NaN, as autograd of the reference's sqrt does.
+__device__ __forceinline__ void v_step_grad(int llh, float vt, float yp, float rho2, float alpha, float& dvt,
+                                            float& drho) {
+    if (llh == GD_LLH_POISSON) {
+        const float t1 = rho2 * vt - alpha;
+        const float s = sqrtf(t1 * t1 + 4.0f * yp * rho2);
+        const float sm = t1 > 0.f ? 4.0f * yp * rho2 / (s + t1) : s - t1;  // s - t1
+        const float ir = 1.0f / rho2;
+        const float v = 0.5f * ir * sm;
+        dvt = -0.5f * sm / s;
+        drho = (yp - rho2 * v * vt) * ir / s - v * ir;
+        return;
+    }
+    const float q = 1.0f / (1.0f + rho2);
+    dvt = rho2 * q;
+    drho = (vt - yp / alpha) * q * q;
 }
 
 // ---------------------------------------------------------------- row-side building blocks
@@ -288,6 +316,40 @@ __device__ __forceinline__ float4 rf_source4(const Args& a, int g, int im, int r
     }
 }
 
+// RF_TRAIN_BWD, the prologue of the training body's adjoint (gd_admm_train_iter_backward): from the incoming
+// gradients a0 = g_zin (last: g_out), a1 = g_u1', a2 = g_w' and the saved vt (a3),
+//   image 0: g_x  = 2 g_zin + g_u1'                      (last: g_out, times alpha for Poisson)
+//   image 1: g_hx = 2 g_vt - g_w',  g_vt = g_w' dV/dvt   (last: 0)
+// o2 receives the pointwise part of g_w, g_w' - g_vt (RI_TRAIN_BWD adds rho2 F^-1(H Q)); acc collects this
+// thread's part of d loss / d rho2_next = sum g_w' dV/drho.
+template <int L>
+__device__ __forceinline__ float4 rf_train_bwd4(const Args& a, int g, int im, size_t pix, float& acc) {
+    if (im == 0) {
+        const float4 gz = ld4(a.a0 + pix);
+        if (a.last) {
+            const float sc = a.llh == GD_LLH_POISSON ? a.alpha(g) : 1.f;
+            return make_float4(gz.x * sc, gz.y * sc, gz.z * sc, gz.w * sc);
+        }
+        const float4 gu = ld4(a.a1 + pix);
+        return make_float4(2.f * gz.x + gu.x, 2.f * gz.y + gu.y, 2.f * gz.z + gu.z, 2.f * gz.w + gu.w);
+    }
+    if (a.last) return make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 gw = ld4(a.a2 + pix), vt = ld4(a.a3 + pix), y = ld4(a.y + pix);
+    const float al = a.alpha(g), r2n = a.rho2n(g);
+    float4 ghx, wp;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float dvt, drho;
+        v_step_grad(a.llh, f4(vt, e), fmaxf(f4(y, e), 0.f), r2n, al, dvt, drho);
+        const float gwe = f4(gw, e), gvt = gwe * dvt;
+        acc += gwe * drho;
+        f4set(ghx, e, 2.f * gvt - gwe);
+        f4set(wp, e, gwe - gvt);
+    }
+    st4(a.o2 + pix, wp);
+    return ghx;
+}
+
 template <int L, int MODE, int RBX = 0>
 __global__ __launch_bounds__((RowGeo<L, RfTraits<MODE>::NI, RBX>::THREADS)) void k_row_fwd(Args a) {
     constexpr int NI = RfTraits<MODE>::NI;
@@ -305,11 +367,32 @@ __global__ __launch_bounds__((RowGeo<L, RfTraits<MODE>::NI, RBX>::THREADS)) void
     fill_twiddles<L>(tw, tid, R::THREADS);
     // stage the block's RB rows of each image through LDS with 16-byte coalesced loads
     float* stage = reinterpret_cast<float*>(lds);  // [im][rr][c]
+    [[maybe_unused]] float acc = 0.f;
     for (int q = tid * 4; q < NI * R::RB * L; q += R::THREADS * 4) {
         const int imq = q / (R::RB * L), rem = q - imq * (R::RB * L);
         const int rr = rem / L, c = rem - rr * L;
         const size_t pix = ((size_t)g * L + row0 + rr) * L + c;
-        st4(stage + q, rf_source4<L, MODE>(a, g, imq, row0 + rr, c, pix));
+        if constexpr (MODE == RF_TRAIN_BWD) st4(stage + q, rf_train_bwd4<L>(a, g, imq, pix, acc));
+        else st4(stage + q, rf_source4<L, MODE>(a, g, imq, row0 + rr, c, pix));
+    }
+    if constexpr (MODE == RF_TRAIN_BWD) {
+        // this block's part of d loss / d rho2_next, summed in a fixed order (no atomics: bit-identical reruns)
+        // -> part[g][2 K + row0]; the block's other rows hold zero, so the caller sums all L entries
+        __shared__ float red[R::THREADS];
+        red[tid] = acc;
+        __syncthreads();
+        if (tid < 64) {
+            float sum = 0.f;
+            for (int i = tid; i < R::THREADS; i += 64) sum += red[i];
+            red[tid] = sum;
+        }
+        __syncthreads();
+        if (tid < R::RB) {
+            float sum = 0.f;
+            if (tid == 0)
+                for (int i = 0; i < (R::THREADS < 64 ? R::THREADS : 64); ++i) sum += red[i];
+            a.part[(size_t)g * (2 * G::K + L) + 2 * G::K + row0 + tid] = sum;
+        }
     }
     __syncthreads();
     float2 v[F2];
@@ -385,11 +468,12 @@ template <int MODE>
 struct ColTraits {
     static constexpr bool IN2 = (MODE == C_ITER || MODE == C_OTF_INIT || MODE == C_OTF_CONV ||
                                  MODE == C_WIENER || MODE == C_CONV2 || MODE == C_TIKHONOV || MODE == C_GX_INIT ||
-                                 MODE == C_GX_BWD);
-    static constexpr bool OUT2 = (MODE == C_ITER || MODE == C_CONV2);
+                                 MODE == C_GX_BWD || MODE == C_TRAIN || MODE == C_TRAIN_BWD);
+    static constexpr bool OUT2 = (MODE == C_ITER || MODE == C_CONV2 || MODE == C_TRAIN || MODE == C_TRAIN_BWD);
     static constexpr bool HAS_OUT = (MODE != C_OTF && MODE != C_FWD && MODE != C_G_W1 && MODE != C_POWER);
     static constexpr bool STORE_OTF = (MODE == C_OTF_INIT || MODE == C_OTF_CONV || MODE == C_OTF);
-    static constexpr bool LOAD_OTF = (MODE == C_ITER || MODE == C_CONV || MODE == C_CONVC || MODE == C_CONV2);
+    static constexpr bool LOAD_OTF = (MODE == C_ITER || MODE == C_CONV || MODE == C_CONVC || MODE == C_CONV2 ||
+                                      MODE == C_TRAIN || MODE == C_TRAIN_BWD);
     static constexpr bool FWD = (MODE != C_INV);
 };
 
@@ -634,8 +718,9 @@ __global__ __launch_bounds__(256) void k_col(Args a) {
     constexpr bool giter = (MODE == C_G_ITER || MODE == C_G_ITER_F || MODE == C_G_ITER_L || MODE == C_G_ITER_FL);
     constexpr bool gfirst = (MODE == C_G_ITER_F || MODE == C_G_ITER_FL);
     constexpr bool glast = (MODE == C_G_ITER_L || MODE == C_G_ITER_FL);
-    const float r1 = (MODE == C_ITER || giter) ? a.rho1(g) : 0.f;
-    const float r2 = (MODE == C_ITER || giter) ? a.rho2(g) : 0.f;
+    constexpr bool train = (MODE == C_TRAIN || MODE == C_TRAIN_BWD);
+    const float r1 = (MODE == C_ITER || giter || train) ? a.rho1(g) : 0.f;
+    const float r2 = (MODE == C_ITER || giter || train) ? a.rho2(g) : 0.f;
     const float r2n = (giter && !glast) ? a.rho2n(g) : 0.f;
 #pragma unroll
     for (int s = 0; s < F2; ++s) {
@@ -646,7 +731,7 @@ __global__ __launch_bounds__(256) void k_col(Args a) {
         if constexpr (TR::STORE_OTF) {
             if (valid) a.otf[ob + ky] = Hk;
         }
-        if constexpr (MODE == C_ITER) {
+        if constexpr (MODE == C_ITER || MODE == C_TRAIN) {
             // runtime X_Update (models/Unrolled_ADMM.py:315-319):
             //   X = (rho1 F(z-u1) + rho2 conj(H) F(v-u2)) / (rho1 |H|^2 + rho2);  HX = H X
             const float HtH = Hk.x * Hk.x + Hk.y * Hk.y;
@@ -654,8 +739,26 @@ __global__ __launch_bounds__(256) void k_col(Args a) {
             const float2 HtW = cmulc(Q[s], Hk);
             const float2 rhs = make_float2(r1 * P[s].x + r2 * HtW.x, r1 * P[s].y + r2 * HtW.y);
             const float2 X = make_float2(rhs.x / lhs, rhs.y / lhs);
+            if constexpr (MODE == C_TRAIN) {
+                // kept for the backward: E = conj(H) W - X = lhs dX/drho2; dX/drho1 = -(rho2 / rho1) dX/drho2
+                // (X is homogeneous of degree 0 in (rho1, rho2)), so this one spectrum serves both
+                if (valid) a.s_w[ob + ky] = csub(HtW, X);
+            }
             P[s] = cscale(X, inv_n);
             Q[s] = cscale(cmul(Hk, X), inv_n);
+        } else if constexpr (MODE == C_TRAIN_BWD) {
+            // adjoint of the X update and of H X: Q = (F(g_x) + conj(H) F(g_hx)) / lhs (1 / lhs real and even:
+            // self-adjoint); out F^-1 Q and F^-1(H Q).  d/drho2 = (1/L^2) sum_k Re(conj(Q) E) over the full
+            // spectrum: half-spectrum bins other than kx = 0, L/2 count twice (as C_GX_BWD)
+            const float HtH = Hk.x * Hk.x + Hk.y * Hk.y;
+            const float lhs = r1 * HtH + r2;
+            const float2 HtG = cmulc(Q[s], Hk);
+            const float2 Qk = make_float2((P[s].x + HtG.x) / lhs, (P[s].y + HtG.y) / lhs);
+            const float2 E = a.s_w[ob + ky];
+            const float wk = (kx == 0 || 2 * kx == L) ? 1.f : 2.f;
+            drho += wk * (Qk.x * E.x + Qk.y * E.y);
+            P[s] = cscale(Qk, inv_n);
+            Q[s] = cscale(cmul(Hk, Qk), inv_n);
         } else if constexpr (MODE == C_OTF_INIT) {
             // init_l2 (models/Unrolled_ADMM.py:170-175): conj(H) F(y/alpha) / (|H|^2 + 1/alpha)
             const float HtH = Hk.x * Hk.x + Hk.y * Hk.y;
@@ -747,6 +850,15 @@ __global__ __launch_bounds__(256) void k_col(Args a) {
 #pragma unroll
         for (int off = F1 / 2; off > 0; off >>= 1) drho += __shfl_xor(drho, off, F1);
         if (valid && j == 0) a.o2[(size_t)g * K + kx] = drho * inv_n;
+    }
+    if constexpr (MODE == C_TRAIN_BWD) {
+#pragma unroll
+        for (int off = F1 / 2; off > 0; off >>= 1) drho += __shfl_xor(drho, off, F1);
+        if (valid && j == 0) {
+            float* pg = a.part + (size_t)g * (2 * K + L);
+            pg[kx] = -(r2 / r1) * (drho * inv_n);  // d/drho1
+            pg[K + kx] = drho * inv_n;             // d/drho2
+        }
     }
     if constexpr (TR::HAS_OUT && MODE != C_FWD && VAR != 1) {
         line_fft<L, true, CLEAN, CDPP>(P, j, my, tw);
@@ -1943,7 +2055,7 @@ __global__ __launch_bounds__(subnet::kThreads, GD_SN_WPE) void k_subnet_rhos_ini
 // ---------------------------------------------------------------- RI: row inverse + sink
 template <int MODE>
 struct RiTraits {
-    static constexpr int NI = (MODE == RI_ITER || MODE == RI_OUT2) ? 2 : 1;
+    static constexpr int NI = (MODE == RI_ITER || MODE == RI_OUT2 || MODE == RI_TRAIN || MODE == RI_TRAIN_BWD) ? 2 : 1;
 };
 
 template <int L, int MODE, int RBX = 0>
@@ -1979,9 +2091,9 @@ __global__ __launch_bounds__((RowGeo<L, RiTraits<MODE>::NI, RBX>::THREADS)) void
     __syncthreads();
 
     float al = 1.f, r2n = 1.f, div = 1.f;
-    if constexpr (MODE == RI_ITER || MODE == RI_INIT) {
+    if constexpr (MODE == RI_ITER || MODE == RI_INIT || MODE == RI_TRAIN) {
         al = a.alpha(g);
-        if (!(MODE == RI_ITER && a.last)) r2n = a.rho2n(g);
+        if (!((MODE == RI_ITER || MODE == RI_TRAIN) && a.last)) r2n = a.rho2n(g);
     }
     if constexpr (MODE == RI_RL_FINAL) div = a.otf[(size_t)g * G::K * L].x;  // conv(Ht, ones) = H(0,0)
     if constexpr (MODE == RI_CROP || MODE == RI_CROP_BWD) {
@@ -2036,6 +2148,49 @@ __global__ __launch_bounds__((RowGeo<L, RiTraits<MODE>::NI, RBX>::THREADS)) void
                 st4(a.o1 + pix, wo);
                 st4(a.o2 + pix, zo);
             }
+        } else if constexpr (MODE == RI_TRAIN) {
+            // RI_ITER out of place (gd_admm_train_iter): u1 (a1) and w (a2) are read-only, u1' -> o0, w' -> o1,
+            // zin' -> o2, and vt = 2 hx - w, the V step's argument, -> o3 for the backward
+            const float4 HX = ld4(res + (R::RB + rr) * L + c);
+            if (a.last) {
+                float4 o = X;
+                if (poisson) o = make_float4(X.x * al, X.y * al, X.z * al, X.w * al);
+                st4(a.o2 + pix, o);
+            } else {
+                const float4 Z = ld4(a.a0 + pix), U1 = ld4(a.a1 + pix), Wv = ld4(a.a2 + pix), Y = ld4(a.y + pix);
+                float4 u1o, wo, zo, vto;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float x = f4(X, e), hx = f4(HX, e);
+                    const float u1 = (f4(U1, e) + x) - f4(Z, e);
+                    const float u2 = hx - f4(Wv, e);
+                    const float vt = hx + u2;
+                    const float vn = v_step(a.llh, vt, fmaxf(f4(Y, e), 0.f), r2n, al);
+                    f4set(u1o, e, u1);
+                    f4set(wo, e, vn - u2);
+                    f4set(zo, e, x + u1);
+                    f4set(vto, e, vt);
+                }
+                st4(a.o0 + pix, u1o);
+                st4(a.o1 + pix, wo);
+                st4(a.o2 + pix, zo);
+                st4(a.o3 + pix, vto);
+            }
+        } else if constexpr (MODE == RI_TRAIN_BWD) {
+            // the adjoint's sink: X = F^-1 Q, image 1 = F^-1(H Q);  g_a = rho1 F^-1 Q,
+            //   g_z = g_a - (g_zin + g_u1'),  g_u1 = (g_zin + g_u1') - g_a,  g_w = (g_w' - g_vt) + rho2 F^-1(H Q)
+            // (o2 holds g_w' - g_vt from RF_TRAIN_BWD; last: g_zin + g_u1' and g_w' - g_vt are zero)
+            const float4 HQ = ld4(res + (R::RB + rr) * L + c);
+            const float r1 = a.rho1(g), r2 = a.rho2(g);
+            float4 sg = make_float4(0.f, 0.f, 0.f, 0.f), wp = sg;
+            if (!a.last) {
+                const float4 gz = ld4(a.a0 + pix), gu = ld4(a.a1 + pix);
+                sg = make_float4(gz.x + gu.x, gz.y + gu.y, gz.z + gu.z, gz.w + gu.w);
+                wp = ld4(a.o2 + pix);
+            }
+            st4(a.o0 + pix, make_float4(r1 * X.x - sg.x, r1 * X.y - sg.y, r1 * X.z - sg.z, r1 * X.w - sg.w));
+            st4(a.o1 + pix, make_float4(sg.x - r1 * X.x, sg.y - r1 * X.y, sg.z - r1 * X.z, sg.w - r1 * X.w));
+            st4(a.o2 + pix, make_float4(wp.x + r2 * HQ.x, wp.y + r2 * HQ.y, wp.z + r2 * HQ.z, wp.w + r2 * HQ.w));
         } else if constexpr (MODE == RI_INIT) {
             // first V step with x = x0, u1 = u2 = 0: v = V(conv(H, x0) + 0, ...)
             const float4 Y = ld4(a.y + pix);
@@ -2453,6 +2608,9 @@ inline Args offset_args(const Args& a, int g0, int n, int H, int W) {
     if (b.o0) b.o0 += img;
     if (b.o1) b.o1 += img;
     if (b.o2) b.o2 += img;
+    if (b.a3) b.a3 += img;
+    if (b.o3) b.o3 += img;
+    if (b.part) b.part += (size_t)g0 * (2 * (W / 2 + 1) + H);
     if (b.psf) b.psf += (long long)g0 * a.psf_gstride;
     GalScalar* gs[] = {&b.alpha, &b.rho1, &b.rho2, &b.rho2n};
     for (GalScalar* x : gs)
@@ -2694,6 +2852,33 @@ struct Ops {
             return Lc::template ri<RI_ITER>(a, st);
         });
     }
+    // Training (gd_admm_train_*): always the chunked chains, whatever the routing switches say
+    static int train_init(Args a0, hipStream_t st0) {
+        // a.otf <- OTF, a.o0 <- x0 = clamp(init_l2), a.o1 <- H x0
+        return for_chunks(a0, L, st0, [&](const Args& a, hipStream_t st) {
+            GD_TRY(Lc::template rf<RF_PSF_Y>(a, st));
+            GD_TRY(Lc::template col<C_OTF_INIT>(a, st));
+            GD_TRY(Lc::template rif<RIF_CLAMP>(a, st));
+            GD_TRY(Lc::template col<C_CONV>(a, st));
+            Args b = a;
+            b.o0 = a.o1;
+            return Lc::template ri<RI_OUT1>(b, st);
+        });
+    }
+    static int train_iter(Args a0, hipStream_t st0) {
+        return for_chunks(a0, L, st0, [&](const Args& a, hipStream_t st) {
+            GD_TRY(Lc::template rf<RF_ITER>(a, st));
+            GD_TRY(Lc::template col<C_TRAIN>(a, st));
+            return Lc::template ri<RI_TRAIN>(a, st);
+        });
+    }
+    static int train_iter_bwd(Args a0, hipStream_t st0) {
+        return for_chunks(a0, L, st0, [&](const Args& a, hipStream_t st) {
+            GD_TRY(Lc::template rf<RF_TRAIN_BWD>(a, st));
+            GD_TRY(Lc::template col<C_TRAIN_BWD>(a, st));
+            return Lc::template ri<RI_TRAIN_BWD>(a, st);
+        });
+    }
     static int wiener(Args a0, hipStream_t st0) {
         return for_chunks(a0, L, st0, [&](const Args& a, hipStream_t st) {
             GD_TRY(Lc::template rf<RF_PSF_RAW>(a, st));
@@ -2878,7 +3063,7 @@ int gd_abi_version(void) { return GD_ABI_VERSION; }
 
 // bumped whenever a kernel's memory traffic changes; PMC summaries are stamped with it so a stale
 // profile is never reported against a different engine
-const char* gd_engine_rev(void) { return "r07.0"; }
+const char* gd_engine_rev(void) { return "r08.0"; }
 
 // the source hash __graft_entry__.build() computed (gdeconv._lib.source_hash); the "gdsrc:" marker lets the
 // build find it in the binary without loading it
@@ -3130,6 +3315,110 @@ int gd_admm_iter_v(const long long* v) {
                         static_cast<const float*>(p(3)), v[4], static_cast<const float*>(p(5)), v[6],
                         static_cast<const float*>(p(7)), v[8], static_cast<const float*>(p(9)), v[10], (int)v[11],
                         (int)v[12], (int)v[13], (int)v[14], (int)v[15], (int)v[16], p(17), p(18), p(19));
+}
+
+// ---------------------------------------------------------------- training: the differentiable loop body
+// saved per iteration: [E = conj(H) W - X, half spectrum N K H complex | vt = 2 H x - w, image N H W floats]
+size_t gd_admm_train_saved_bytes(int N, int H, int W) {
+    if (!gd_supported_size(H, W) || N <= 0) return 0;
+    return (size_t)N * (W / 2 + 1) * H * sizeof(float2) + (size_t)N * H * W * sizeof(float);
+}
+
+int gd_admm_train_init(const float* y, const float* psf, long long psf_gstride, int h, int w, const float* alpha,
+                       long long alpha_stride, int N, int H, int W, void* otf_half, float* x0, float* hx0, void* ws,
+                       void* stream) {
+    GD_TRY(check_shape(N, H, W));
+    GD_TRY(check_psf(h, w, H, W));
+    if (!y || !psf || !alpha || !otf_half || !x0 || !hx0 || !ws) return fail(GD_ERR_ARG, "gd_admm_train_init: null pointer");
+    if (x0 == hx0 || x0 == y || hx0 == y) return fail(GD_ERR_ARG, "gd_admm_train_init: x0, hx0 and y must be distinct buffers");
+    if (N == 0) return GD_OK;
+    Args a = base_args(N, ws, H, W);
+    a.y = y; a.psf = psf; a.psf_gstride = psf_gstride; a.h = h;
+    a.alpha = GalScalar{alpha, alpha_stride};
+    a.otf = reinterpret_cast<float2*>(otf_half);
+    a.o0 = x0; a.o1 = hx0;
+    ProfScope ps("op_admm_train_init<" + std::to_string(H) + ">", (hipStream_t)stream, 1);
+    return dispatch<Ops>(H, W, [&](auto op) { return decltype(op)::train_init(a, (hipStream_t)stream); });
+}
+
+int gd_admm_train_iter(const float* y, const float* z, const float* u1, const float* w, const float* alpha,
+                       long long alpha_stride, const float* rho1, long long rho1_stride, const float* rho2,
+                       long long rho2_stride, const float* rho2_next, long long rho2_next_stride, int llh, int last,
+                       int N, int H, int W, const void* otf_half, float* zin_or_out, float* u1_out, float* w_out,
+                       void* saved, void* ws, void* stream) {
+    GD_TRY(check_shape(N, H, W));
+    if (llh != GD_LLH_GAUSSIAN && llh != GD_LLH_POISSON) return fail(GD_ERR_ARG, "llh must be Gaussian or Poisson");
+    if (!y || !z || !u1 || !w || !alpha || !rho1 || !rho2 || !otf_half || !zin_or_out || !saved || !ws)
+        return fail(GD_ERR_ARG, "gd_admm_train_iter: null pointer");
+    if (!last && (!rho2_next || !u1_out || !w_out))
+        return fail(GD_ERR_ARG, "gd_admm_train_iter: rho2_next, u1_out and w_out required unless last");
+    {
+        // out of place: the inputs stay as the graph's upstream nodes hold them, and the outputs are three buffers
+        const void* in[] = {y, z, u1, w};
+        const void* out[] = {zin_or_out, last ? nullptr : u1_out, last ? nullptr : w_out, saved};
+        for (int i = 0; i < 4; ++i) {
+            if (!out[i]) continue;
+            for (const void* p : in)
+                if (out[i] == p) return fail(GD_ERR_ARG, "gd_admm_train_iter: an output aliases an input (the body is out of place)");
+            for (int k = 0; k < i; ++k)
+                if (out[i] == out[k]) return fail(GD_ERR_ARG, "gd_admm_train_iter: two outputs share a buffer");
+        }
+    }
+    if (N == 0) return GD_OK;
+    Args a = base_args(N, ws, H, W);
+    a.y = y; a.a0 = z; a.a1 = u1; a.a2 = w;
+    a.alpha = GalScalar{alpha, alpha_stride};
+    a.rho1 = GalScalar{rho1, rho1_stride};
+    a.rho2 = GalScalar{rho2, rho2_stride};
+    a.rho2n = GalScalar{rho2_next ? rho2_next : rho2, rho2_next ? rho2_next_stride : rho2_stride};
+    a.llh = llh;
+    a.last = last != 0;
+    a.otf = reinterpret_cast<float2*>(const_cast<void*>(otf_half));
+    a.o0 = u1_out; a.o1 = w_out; a.o2 = zin_or_out;
+    a.s_w = reinterpret_cast<float2*>(saved);
+    a.o3 = reinterpret_cast<float*>(a.s_w + (size_t)N * (W / 2 + 1) * H);
+    ProfScope ps("op_admm_train_iter<" + std::to_string(H) + "," + std::to_string(llh) + ">", (hipStream_t)stream, 1);
+    return dispatch<Ops>(H, W, [&](auto op) { return decltype(op)::train_iter(a, (hipStream_t)stream); });
+}
+
+int gd_admm_train_iter_backward(const float* g_zin_or_out, const float* g_u1_out, const float* g_w_out, const float* y,
+                                const float* alpha, long long alpha_stride, const float* rho1, long long rho1_stride,
+                                const float* rho2, long long rho2_stride, const float* rho2_next,
+                                long long rho2_next_stride, int llh, int last, int N, int H, int W, const void* otf_half,
+                                const void* saved, float* g_z, float* g_u1, float* g_w, float* g_rho_part, void* ws,
+                                void* stream) {
+    GD_TRY(check_shape(N, H, W));
+    if (llh != GD_LLH_GAUSSIAN && llh != GD_LLH_POISSON) return fail(GD_ERR_ARG, "llh must be Gaussian or Poisson");
+    if (!g_zin_or_out || !y || !alpha || !rho1 || !rho2 || !otf_half || !saved || !g_z || !g_u1 || !g_w || !g_rho_part || !ws)
+        return fail(GD_ERR_ARG, "gd_admm_train_iter_backward: null pointer");
+    if (!last && (!rho2_next || !g_u1_out || !g_w_out))
+        return fail(GD_ERR_ARG, "gd_admm_train_iter_backward: rho2_next, g_u1_out and g_w_out required unless last");
+    {
+        const void* in[] = {g_zin_or_out, g_u1_out, g_w_out, y, saved};
+        const void* out[] = {g_z, g_u1, g_w, g_rho_part};
+        for (int i = 0; i < 4; ++i) {
+            for (const void* p : in)
+                if (out[i] == p) return fail(GD_ERR_ARG, "gd_admm_train_iter_backward: an output aliases an input");
+            for (int k = 0; k < i; ++k)
+                if (out[i] == out[k]) return fail(GD_ERR_ARG, "gd_admm_train_iter_backward: two outputs share a buffer");
+        }
+    }
+    if (N == 0) return GD_OK;
+    Args a = base_args(N, ws, H, W);
+    a.y = y; a.a0 = g_zin_or_out; a.a1 = g_u1_out; a.a2 = g_w_out;
+    a.alpha = GalScalar{alpha, alpha_stride};
+    a.rho1 = GalScalar{rho1, rho1_stride};
+    a.rho2 = GalScalar{rho2, rho2_stride};
+    a.rho2n = GalScalar{rho2_next ? rho2_next : rho2, rho2_next ? rho2_next_stride : rho2_stride};
+    a.llh = llh;
+    a.last = last != 0;
+    a.otf = reinterpret_cast<float2*>(const_cast<void*>(otf_half));
+    a.s_w = reinterpret_cast<float2*>(const_cast<void*>(saved));
+    a.a3 = reinterpret_cast<const float*>(a.s_w + (size_t)N * (W / 2 + 1) * H);
+    a.o0 = g_z; a.o1 = g_u1; a.o2 = g_w;
+    a.part = g_rho_part;
+    ProfScope ps("op_admm_train_bwd<" + std::to_string(H) + "," + std::to_string(llh) + ">", (hipStream_t)stream, 1);
+    return dispatch<Ops>(H, W, [&](auto op) { return decltype(op)::train_iter_bwd(a, (hipStream_t)stream); });
 }
 
 int gd_wiener(const float* y, const float* psf, long long psf_gstride, int h, int w, const float* alpha,

@@ -288,6 +288,22 @@ __device__ __forceinline__ float gsrc(const Args& a, const Dims& d, int g, int i
     }
 }
 
+// RF_TRAIN_BWD's producer (gd_engine.hip rf_train_bwd4), one pixel at a time
+__device__ __forceinline__ float gsrc_train_bwd(const Args& a, const Dims& d, int g, int im, int r, int c, float& acc) {
+    const size_t pix = ((size_t)g * d.H + r) * d.W + c;
+    if (im == 0) {
+        if (a.last) return a.llh == GD_LLH_POISSON ? a.a0[pix] * a.alpha(g) : a.a0[pix];  // g_out (x alpha)
+        return 2.f * a.a0[pix] + a.a1[pix];                                               // 2 g_zin + g_u1'
+    }
+    if (a.last) return 0.f;
+    float dvt, drho;
+    v_step_grad(a.llh, a.a3[pix], fmaxf(a.y[pix], 0.f), a.rho2n(g), a.alpha(g), dvt, drho);
+    const float gw = a.a2[pix], gvt = gw * dvt;
+    acc += gw * drho;
+    a.o2[pix] = gw - gvt;       // the pointwise part of g_w
+    return 2.f * gvt - gw;      // g_hx
+}
+
 // rows 2 pr, 2 pr + 1 of image im (pr = p0 + mm) -> line im pb + mm; the spectra of each image's rows
 // from the packed line spectra C: row 2m (C + conj D)/2, row 2m+1 (C - conj D)/(2i), D = C[(W - k) mod W]
 __device__ __forceinline__ void gsplit_store(const Args& a, const Dims& d, const float2* res, int g, int p0, int pb,
@@ -341,12 +357,35 @@ __global__ __launch_bounds__(kThreads) void k_gen_rf(Args a, Dims d) {
     float2* x = gsm + W;
     float2* y = x + nl * W;
     fill_tw(tw, W);
+    [[maybe_unused]] float acc = 0.f;
     for (int e = threadIdx.x; e < nl * W; e += blockDim.x) {
         const int line = e / W, c = e - line * W;
         const int im = line / pb, r0 = 2 * (p0 + line - im * pb);
-        const float v0 = r0 < H ? gsrc<MODE>(a, d, g, im, r0, c) : 0.f;
-        const float v1 = r0 + 1 < H ? gsrc<MODE>(a, d, g, im, r0 + 1, c) : 0.f;
+        float v0 = 0.f, v1 = 0.f;
+        if constexpr (MODE == RF_TRAIN_BWD) {
+            if (r0 < H) v0 = gsrc_train_bwd(a, d, g, im, r0, c, acc);
+            if (r0 + 1 < H) v1 = gsrc_train_bwd(a, d, g, im, r0 + 1, c, acc);
+        } else {
+            if (r0 < H) v0 = gsrc<MODE>(a, d, g, im, r0, c);
+            if (r0 + 1 < H) v1 = gsrc<MODE>(a, d, g, im, r0 + 1, c);
+        }
         x[e] = make_float2(v0, v1);
+    }
+    if constexpr (MODE == RF_TRAIN_BWD) {
+        // this block's part of d loss / d rho2_next in a fixed order -> part[g][2 K + first row]; its other rows zero
+        // (kThreads = 4 full waves; the wave sums pass through the still unused second line buffer: no static LDS
+        // next to a dynamic allocation that may fill the 64 KiB)
+        float* red = reinterpret_cast<float*>(y);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        for (int rr = threadIdx.x; rr < 2 * pb && 2 * p0 + rr < H; rr += blockDim.x) {
+            float sum = 0.f;
+            if (rr == 0)
+                for (int i = 0; i < kThreads / 64; ++i) sum += red[i];
+            a.part[(size_t)g * (2 * d.K + H) + 2 * d.K + 2 * p0 + rr] = sum;
+        }
     }
     __syncthreads();
     const float2* res = fft_lines(x, y, d.row, tw, nl, false);
@@ -394,7 +433,7 @@ __global__ __launch_bounds__(kThreads) void k_gen_col(Args a, Dims d) {
     for (int e = threadIdx.x; e < cb * H; e += blockDim.x) {
         const int cc = e / H, ky = e - cc * H, f = f0 + cc;
         if (f >= NK) {
-            if constexpr (MODE == C_GX_BWD) part[e] = 0.f;
+            if constexpr (MODE == C_GX_BWD || MODE == C_TRAIN_BWD) part[e] = 0.f;
             continue;
         }
         const int g = f / K, kx = f - g * K;
@@ -406,7 +445,7 @@ __global__ __launch_bounds__(kThreads) void k_gen_col(Args a, Dims d) {
         if constexpr (TR::LOAD_OTF) Hk = a.otf[(a.otf_bcast ? (size_t)kx * H : ob) + ky];
         if constexpr (TR::STORE_OTF || MODE == C_WIENER || MODE == C_TIKHONOV) Hk = Pv;
         if constexpr (TR::STORE_OTF) a.otf[o] = Hk;
-        if constexpr (MODE == C_ITER) {
+        if constexpr (MODE == C_ITER || MODE == C_TRAIN) {
             // runtime X_Update (models/Unrolled_ADMM.py:315-319): X = (rho1 F(z-u1) + rho2 conj(H) F(w)) / lhs
             const float r1 = a.rho1(g), r2 = a.rho2(g);
             const float HtH = Hk.x * Hk.x + Hk.y * Hk.y;
@@ -414,8 +453,21 @@ __global__ __launch_bounds__(kThreads) void k_gen_col(Args a, Dims d) {
             const float2 HtW = cmulc(Qv, Hk);
             const float2 rhs = make_float2(r1 * Pv.x + r2 * HtW.x, r1 * Pv.y + r2 * HtW.y);
             const float2 X = make_float2(rhs.x / lhs, rhs.y / lhs);
+            if constexpr (MODE == C_TRAIN) a.s_w[o] = csub(HtW, X);  // E = conj(H) W - X, kept for the backward
             Pv = cscale(X, inv_n);
             P[(cb + cc) * H + ky] = cscale(cmul(Hk, X), inv_n);
+        } else if constexpr (MODE == C_TRAIN_BWD) {
+            // adjoint of the X update and of H X (gd_engine.hip C_TRAIN_BWD); d/drho2 terms over the full spectrum
+            const float r1 = a.rho1(g), r2 = a.rho2(g);
+            const float HtH = Hk.x * Hk.x + Hk.y * Hk.y;
+            const float lhs = r1 * HtH + r2;
+            const float2 HtG = cmulc(Qv, Hk);
+            const float2 Qk = make_float2((Pv.x + HtG.x) / lhs, (Pv.y + HtG.y) / lhs);
+            const float2 E = a.s_w[o];
+            const float wk = (kx == 0 || 2 * kx == W) ? 1.f : 2.f;
+            part[e] = wk * (Qk.x * E.x + Qk.y * E.y);
+            Pv = cscale(Qk, inv_n);
+            P[(cb + cc) * H + ky] = cscale(cmul(Hk, Qk), inv_n);
         } else if constexpr (MODE == C_OTF_INIT) {
             // init_l2 (models/Unrolled_ADMM.py:170-175): conj(H) F(y/alpha) / (|H|^2 + 1/alpha)
             const float HtH = Hk.x * Hk.x + Hk.y * Hk.y;
@@ -510,6 +562,17 @@ __global__ __launch_bounds__(kThreads) void k_gen_col(Args a, Dims d) {
         }
         __syncthreads();
     }
+    if constexpr (MODE == C_TRAIN_BWD) {
+        if ((int)threadIdx.x < cb && f0 + (int)threadIdx.x < NK) {  // fixed-order sum per column
+            const int f = f0 + threadIdx.x, g = f / K, kx = f - g * K;
+            float s = 0.f;
+            for (int ky = 0; ky < H; ++ky) s += part[threadIdx.x * H + ky];
+            float* pg = a.part + (size_t)g * (2 * K + H);
+            pg[kx] = -(a.rho2(g) / a.rho1(g)) * (s * inv_n);  // d/drho1 (X is homogeneous of degree 0 in the rhos)
+            pg[K + kx] = s * inv_n;                           // d/drho2
+        }
+        __syncthreads();
+    }
     if constexpr (MODE == C_FWD) {
         for (int e = threadIdx.x; e < cb * H; e += blockDim.x) {
             const int cc = e / H, ky = e - cc * H, f = f0 + cc;
@@ -543,9 +606,9 @@ __global__ __launch_bounds__(kThreads) void k_gen_ri(Args a, Dims d) {
     __syncthreads();
     const float2* res = fft_lines(x, y, d.row, tw, nl, true);
     float al = 1.f, r2n = 1.f, div = 1.f;
-    if constexpr (MODE == RI_ITER || MODE == RI_INIT) {
+    if constexpr (MODE == RI_ITER || MODE == RI_INIT || MODE == RI_TRAIN) {
         al = a.alpha(g);
-        if (!(MODE == RI_ITER && a.last)) r2n = a.rho2n(g);
+        if (!((MODE == RI_ITER || MODE == RI_TRAIN) && a.last)) r2n = a.rho2n(g);
     }
     if constexpr (MODE == RI_RL_FINAL) div = a.otf[(size_t)g * K * H].x;  // conv(Ht, ones) = H(0,0)
     const bool poisson = a.llh == GD_LLH_POISSON;
@@ -584,6 +647,32 @@ __global__ __launch_bounds__(kThreads) void k_gen_ri(Args a, Dims d) {
                 a.o1[pix] = vn - u2;
                 a.o2[pix] = X + u1;                                      // next denoiser input
             }
+        } else if constexpr (MODE == RI_TRAIN) {
+            // RI_ITER out of place: u1 (a1), w (a2) read-only; u1' -> o0, w' -> o1, zin' -> o2, vt -> o3 (saved)
+            const float2 v1 = res[(pb + (rr >> 1)) * W + c];
+            const float hx = (rr & 1) ? v1.y : v1.x;
+            if (a.last) {
+                a.o2[pix] = poisson ? X * al : X;
+            } else {
+                const float u1 = (a.a1[pix] + X) - a.a0[pix];
+                const float u2 = hx - a.a2[pix];
+                const float vt = hx + u2;
+                const float vn = v_step(a.llh, vt, fmaxf(a.y[pix], 0.f), r2n, al);
+                a.o0[pix] = u1;
+                a.o1[pix] = vn - u2;
+                a.o2[pix] = X + u1;
+                a.o3[pix] = vt;
+            }
+        } else if constexpr (MODE == RI_TRAIN_BWD) {
+            // the adjoint's sink (gd_engine.hip RI_TRAIN_BWD): X = F^-1 Q, image 1 = F^-1(H Q)
+            const float2 v1 = res[(pb + (rr >> 1)) * W + c];
+            const float hq = (rr & 1) ? v1.y : v1.x;
+            const float ga = a.rho1(g) * X;
+            const float sg = a.last ? 0.f : a.a0[pix] + a.a1[pix];
+            const float wp = a.last ? 0.f : a.o2[pix];
+            a.o0[pix] = ga - sg;
+            a.o1[pix] = sg - ga;
+            a.o2[pix] = wp + a.rho2(g) * hq;
         } else if constexpr (MODE == RI_INIT) {
             a.o1[pix] = v_step(a.llh, X + 0.0f, fmaxf(a.y[pix], 0.f), r2n, al);
             a.o0[pix] = 0.f;
@@ -795,6 +884,32 @@ struct GOps {
             GD_TRY(Lc::rf<RF_ITER>(a, st));
             GD_TRY(Lc::col<C_ITER>(a, st));
             return Lc::ri<RI_ITER>(a, st);
+        });
+    }
+    // Training (gd_admm_train_*): the chunked chains, independent of the routing switches
+    static int train_init(Args a0, hipStream_t st0) {
+        return chunks(a0, st0, [&](const Args& a, hipStream_t st) {
+            GD_TRY(Lc::rf<RF_PSF_Y>(a, st));
+            GD_TRY(Lc::col<C_OTF_INIT>(a, st));
+            GD_TRY(Lc::rif<RIF_CLAMP>(a, st));
+            GD_TRY(Lc::col<C_CONV>(a, st));
+            Args b = a;
+            b.o0 = a.o1;
+            return Lc::ri<RI_OUT1>(b, st);
+        });
+    }
+    static int train_iter(Args a0, hipStream_t st0) {
+        return chunks(a0, st0, [&](const Args& a, hipStream_t st) {
+            GD_TRY(Lc::rf<RF_ITER>(a, st));
+            GD_TRY(Lc::col<C_TRAIN>(a, st));
+            return Lc::ri<RI_TRAIN>(a, st);
+        });
+    }
+    static int train_iter_bwd(Args a0, hipStream_t st0) {
+        return chunks(a0, st0, [&](const Args& a, hipStream_t st) {
+            GD_TRY(Lc::rf<RF_TRAIN_BWD>(a, st));
+            GD_TRY(Lc::col<C_TRAIN_BWD>(a, st));
+            return Lc::ri<RI_TRAIN_BWD>(a, st);
         });
     }
     static int wiener(Args a0, hipStream_t st0) {

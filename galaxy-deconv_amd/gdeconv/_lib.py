@@ -48,6 +48,12 @@ SIGNATURES = {
     "gd_admm_iter_tail_v": (_I, [_P]),
     "gd_admm_tail_supported": (_I, [_I, _I, _I, _I]),
     "gd_set_combined_tail": (_I, [_I]),
+    "gd_admm_train_saved_bytes": (_SZ, [_I, _I, _I]),
+    "gd_admm_train_init": (_I, [_P, _P, _LL, _I, _I, _P, _LL, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "gd_admm_train_iter": (_I, [_P, _P, _P, _P, _P, _LL, _P, _LL, _P, _LL, _P, _LL, _I, _I, _I, _I, _I, _P, _P, _P,
+                                _P, _P, _P, _P]),
+    "gd_admm_train_iter_backward": (_I, [_P, _P, _P, _P, _P, _LL, _P, _LL, _P, _LL, _P, _LL, _I, _I, _I, _I, _I, _P,
+                                         _P, _P, _P, _P, _P, _P, _P]),
     "gd_wiener": (_I, [_P, _P, _LL, _I, _I, _P, _LL, _P, _I, _I, _I, _P, _P]),
     "gd_richardson_lucy": (_I, [_P, _P, _LL, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
     "gd_tikhonov": (_I, [_P, _P, _LL, _I, _I, _P, _LL, _P, _LL, _P, _LL, _P, _I, _I, _I, _P, _P]),

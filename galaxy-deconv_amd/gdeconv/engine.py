@@ -784,7 +784,135 @@ class ADMMState:
         return dst
 
 
+class ADMMTrainState:
+    """What one differentiable ``Unrolled_ADMM`` forward shares between its iterations
+    (models/Unrolled_ADMM.py:177-196): the half-spectrum OTF, ``x0 = clamp(init_l2)`` and ``hx0 = conv_fft_batch(H,
+    x0)`` (gd_admm_train_init, computed at construction), y, alpha and the likelihood.  None of them carries a
+    gradient.  The iteration state itself (zin, u1, w = v - u2) lives in the autograd graph: ``admm_train_iter``."""
+
+    def __init__(self, y, psf, alpha, llh):
+        self.dev = _require_device(y, psf, alpha)
+        self.lib = _lib.load()
+        self.y = _img(y.detach(), "y")
+        self.N, _, self.H, self.W = self.y.shape
+        self.psf, self.psf_gs = _psf(psf.detach(), self.N, self.H)
+        if llh not in _lib.GD_LLH:
+            raise ValueError("llh must be 'Gaussian' or 'Poisson'")
+        self.llh_name, self.llh = llh, _lib.GD_LLH[llh]
+        if not self.lib.gd_supported_size(self.H, self.W):
+            raise ValueError(f"unsupported image size {self.H}x{self.W} (H and W must be in [2, 4096])")
+        self.saved_bytes = int(self.lib.gd_admm_train_saved_bytes(max(self.N, 1), self.H, self.W))
+        self.K = self.W // 2 + 1
+        k = self.psf
+        with _on(self.dev):
+            self.alpha, self.alpha_s = _galaxy_scalar(alpha.detach() if torch.is_tensor(alpha) else alpha, self.N,
+                                                      "alpha", self.dev)
+            self.otf = empty_otf(self.N, self.H, self.W, self.dev)
+            self.x0, self.hx0 = torch.empty_like(self.y), torch.empty_like(self.y)
+            _lib.check(self.lib.gd_admm_train_init(
+                self.y.data_ptr(), k.data_ptr(), self.psf_gs, k.shape[2], k.shape[3], self.alpha.data_ptr(),
+                self.alpha_s, self.N, self.H, self.W, self.otf.data_ptr(), self.x0.data_ptr(), self.hx0.data_ptr(),
+                workspace(self.N, self.H, self.W, self.dev).data_ptr(), _stream(self.dev)), "gd_admm_train_init")
+
+    def alpha4(self):
+        """alpha as it broadcasts against [N,1,H,W] images."""
+        return self.alpha.view(-1, 1, 1, 1)
+
+    def w0(self, rho2_first):
+        """w_0 = V(hx0; rho2[0]) (u2 = 0), differentiable in ``rho2_first``: the first V step (:207), once per
+        forward, as PyTorch elementwise ops."""
+        yp, al = self.y.clamp_min(0.0), self.alpha4()
+        if self.llh_name == "Poisson":
+            t1 = rho2_first * self.hx0 - al
+            return 0.5 * (1 / rho2_first) * (-t1 + torch.sqrt(t1 ** 2 + 4 * yp * rho2_first))
+        return (rho2_first * self.hx0 + yp / al) / (1 + rho2_first)
+
+    def rho(self, t):
+        """(keep-alive tensor, device pointer, galaxy stride) of one iteration's penalty: a [N,1,1,1] view of the
+        SubNet output (used in place through its stride), a 0-dim / 1-element entry of ``rho*_iters``, or a number."""
+        if torch.is_tensor(t):
+            t = t.detach()
+            if t.device != self.dev:
+                raise ValueError(f"rho is on {t.device}, the inputs on {self.dev}")
+            if t.dtype == torch.float32 and t.dim() == 4 and t.shape[0] == self.N and t.numel() == self.N and self.N > 1:
+                return t, t.data_ptr(), t.stride(0)
+        t, s = _galaxy_scalar(t, self.N, "rho", self.dev)
+        return t, t.data_ptr(), s
+
+
+class _ADMMTrainIterFn(torch.autograd.Function):
+    """One ``Unrolled_ADMM`` loop body on the engine (gd_admm_train_iter) with its HIP adjoint
+    (gd_admm_train_iter_backward).  Each call owns its saved buffer (one half spectrum and one image)."""
+
+    @staticmethod
+    def forward(ctx, z, u1, w, rho1, rho2, rho2_next, st, last):
+        N, H, W, dev = st.N, st.H, st.W, st.dev
+        shape = tuple(st.y.shape)
+        ins = []
+        for t, name in ((z, "z"), (u1, "u1"), (w, "w")):
+            t = _img(t.detach(), name)
+            if tuple(t.shape) != shape or t.device != dev:
+                raise ValueError(f"{name} must be {shape} on {dev}, got {tuple(t.shape)} on {t.device}")
+            ins.append(t)
+        r1 = st.rho(rho1)
+        r2 = st.rho(rho2)
+        r2n = st.rho(rho2_next) if not last else (None, None, 0)
+        with _on(dev):
+            zin = torch.empty_like(st.y)
+            u1o = None if last else torch.empty_like(st.y)
+            wo = None if last else torch.empty_like(st.y)
+            saved = torch.empty(st.saved_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(st.lib.gd_admm_train_iter(
+                st.y.data_ptr(), ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(), st.alpha.data_ptr(),
+                st.alpha_s, r1[1], r1[2], r2[1], r2[2], r2n[1], r2n[2], st.llh, int(last), N, H, W,
+                st.otf.data_ptr(), zin.data_ptr(), None if last else u1o.data_ptr(), None if last else wo.data_ptr(),
+                saved.data_ptr(), workspace(N, H, W, dev).data_ptr(), _stream(dev)), "gd_admm_train_iter")
+        ctx.st, ctx.last, ctx.saved, ctx.rhos = st, last, saved, (r1, r2, r2n)
+        ctx.rho_meta = [(t.shape, t.dtype) if torch.is_tensor(t) else None for t in (rho1, rho2, rho2_next)]
+        return zin if last else (zin, u1o, wo)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        st, last = ctx.st, ctx.last
+        N, H, W, K, dev = st.N, st.H, st.W, st.K, st.dev
+        r1, r2, r2n = ctx.rhos
+        g = [None if t is None else t.float().contiguous() for t in grads]
+        with _on(dev):
+            gz, gu1, gw = torch.empty_like(st.y), torch.empty_like(st.y), torch.empty_like(st.y)
+            part = torch.empty(N, 2 * K + H, dtype=torch.float32, device=dev)
+            _lib.check(st.lib.gd_admm_train_iter_backward(
+                g[0].data_ptr(), None if last else g[1].data_ptr(), None if last else g[2].data_ptr(),
+                st.y.data_ptr(), st.alpha.data_ptr(), st.alpha_s, r1[1], r1[2], r2[1], r2[2], r2n[1], r2n[2], st.llh,
+                int(last), N, H, W, st.otf.data_ptr(), ctx.saved.data_ptr(), gz.data_ptr(), gu1.data_ptr(),
+                gw.data_ptr(), part.data_ptr(), workspace(N, H, W, dev).data_ptr(), _stream(dev)),
+                "gd_admm_train_iter_backward")
+        groups = (part[:, :K], part[:, K:2 * K], part[:, 2 * K:])
+        grho = []
+        for i, meta in enumerate(ctx.rho_meta):
+            if meta is None or not ctx.needs_input_grad[3 + i]:
+                grho.append(None)
+                continue
+            shp, dt = meta
+            gg = groups[i].sum(1)                     # per galaxy
+            n_el = 1
+            for s in shp:
+                n_el *= s
+            gg = gg.sum() if n_el == 1 else gg        # a shared rho: the sum over galaxies
+            grho.append(gg.reshape(shp).to(dt))
+        return (gz if ctx.needs_input_grad[0] else None, gu1 if ctx.needs_input_grad[1] else None,
+                gw if ctx.needs_input_grad[2] else None, grho[0], grho[1], grho[2], None, None)
+
+
+def admm_train_iter(st, z, u1, w, rho1, rho2, rho2_next, last):
+    """One differentiable loop body of ``Unrolled_ADMM`` (models/Unrolled_ADMM.py:199-215) after the denoiser
+    returned ``z``: ``(zin', u1', w')``, or the output x (times alpha for Poisson) when ``last``.  Gradients flow to
+    z, u1, w and the rhos ([N,1,1,1] views or 0-dim entries of a shared schedule, whose gradient is the sum over
+    galaxies); ``st`` is the forward's ``ADMMTrainState``.  ``rho2_next`` is ignored when ``last``."""
+    return _ADMMTrainIterFn.apply(z, u1, w, rho1, rho2, None if last else rho2_next, st, bool(last))
+
+
 __all__ = ["psf_to_otf_half", "conv_half", "rfft2_half", "irfft2_half", "wiener", "richardson_lucy",
            "tikhonov", "filter_power", "filter_power_taps", "GaussXState", "gx_x_update",
+           "ADMMTrainState", "admm_train_iter",
            "ADMMState", "RhoSchedule", "workspace", "empty_otf", "supported", "subnet_features", "subnet_rhos", "subnet_rhos_psf",
            "mlp_supported"]

@@ -19,10 +19,17 @@ reference builds it on the CPU every forward, ``utils/utils_torch.py:81``), CPU 
 rejected (no CPU path), unsupported reference variants raise instead of misbehaving
 (``PnP=False``: the reference's l1 ``Z_Update`` call uses an undefined ``lam``, ``:208``), and
 ``Unrolled_ADMM`` is inference-only: in training mode its forward raises under autograd when a
-parameter requires grad (the engine writes through raw pointers, so no graph would reach ``self.Z`` /
-``self.init``; the differentiable variant is ``UnrolledADMMGaussian``, whose X update has a HIP
-backward); in eval mode it runs under ``torch.no_grad()`` and returns an output without a graph (only
+parameter requires grad (its engine calls update the state in place through raw pointers, so no graph would
+reach ``self.Z`` / ``self.init``; train ``TrainableUnrolledADMM`` below, or ``UnrolledADMMGaussian``, whose X
+update has a HIP backward); in eval mode it runs under ``torch.no_grad()`` and returns an output without a graph (only
 parameter gradients can be dropped that way: an input ``y`` / ``kernel`` / ``alpha`` that requires grad raises).
+
+* ``TrainableUnrolledADMM(...)`` - ``Unrolled_ADMM`` with the same constructor, attributes and ``state_dict``
+  keys (checkpoints move between the two), differentiable: with autograd on and a parameter that requires grad,
+  every loop body is one ``engine.admm_train_iter`` (out-of-place HIP body + HIP adjoint, both likelihoods, every
+  supported size), so the output's graph reaches ``Z``, ``init`` and ``rho1_iters`` / ``rho2_iters``.  Under
+  ``torch.no_grad()`` or with nothing to differentiate it is the parent's fast path.  No gradient to
+  ``y`` / ``kernel`` / ``alpha`` (such inputs raise).
 """
 import warnings
 
@@ -72,7 +79,8 @@ class Unrolled_ADMM(nn.Module):
             if self.training:
                 raise NotImplementedError(
                     "Unrolled_ADMM on the HIP engine is inference-only (call .eval(), wrap the call in "
-                    "torch.no_grad() or freeze the parameters); train UnrolledADMMGaussian, whose X update "
+                    "torch.no_grad() or freeze the parameters); train TrainableUnrolledADMM (same constructor and "
+                    "state_dict keys, HIP backward of the loop body) or UnrolledADMMGaussian, whose X update "
                     "has a HIP backward")
             # eval mode with grad enabled (e.g. figures/grid_plot.ipynb calls the model and .detach()es):
             # the output carries no graph, as documented above
@@ -132,6 +140,38 @@ class Unrolled_ADMM(nn.Module):
             st.step(z, r1[it], r2[it], r2[it + 1] if it + 1 < n else None, out=out,
                     rho1_next=r1[it + 1] if it == n - 2 else None)
         return out
+
+
+class TrainableUnrolledADMM(Unrolled_ADMM):
+    """``Unrolled_ADMM`` that can be trained and fine-tuned on the engine (models/Unrolled_ADMM.py:177-215 is
+    differentiable in the reference).  Same constructor, attributes and ``state_dict`` keys.  With autograd on and a
+    parameter that requires grad, the forward keeps the iteration state (zin, u1, w = v - u2) as images in the
+    autograd graph and runs each loop body through ``engine.admm_train_iter``; otherwise it is the parent's
+    inference path, unchanged."""
+
+    def forward(self, y, kernel, alpha):
+        if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (y, kernel, alpha)):
+            raise NotImplementedError(
+                "TrainableUnrolledADMM differentiates with respect to its parameters only: an input requires grad "
+                "(detach it); the HIP backward carries no gradient to y, the PSF or alpha")
+        if not (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
+            return self._forward(y, kernel, alpha)
+        st = engine.ADMMTrainState(y, kernel, alpha, self.llh)   # rejects CPU tensors before anything runs
+        n = self.n
+        if n == 0:
+            return st.x0 * st.alpha4() if self.llh == "Poisson" else st.x0
+        rho1_iters, rho2_iters = self.rhos(kernel, alpha)
+
+        def pick(r, i):   # models/Unrolled_ADMM.py:201-206
+            return r[:, :, :, i].view(-1, 1, 1, 1) if r.dim() == 4 else r[i]
+
+        zin, u1, w = st.x0, torch.zeros_like(st.x0), st.w0(pick(rho2_iters, 0))
+        for it in range(n):
+            z = self.Z(zin)
+            if it == n - 1:
+                return engine.admm_train_iter(st, z, u1, w, pick(rho1_iters, it), pick(rho2_iters, it), None, True)
+            zin, u1, w = engine.admm_train_iter(st, z, u1, w, pick(rho1_iters, it), pick(rho2_iters, it),
+                                                pick(rho2_iters, it + 1), False)
 
 
 class Wiener(nn.Module):
@@ -268,5 +308,6 @@ class Tikhonet(nn.Module):
         return x * alpha
 
 
-__all__ = ["Unrolled_ADMM", "UnrolledADMMGaussian", "XUpdateGaussian", "Wiener", "Richard_Lucy", "Tikhonov",
+__all__ = ["Unrolled_ADMM", "TrainableUnrolledADMM", "UnrolledADMMGaussian", "XUpdateGaussian", "Wiener",
+           "Richard_Lucy", "Tikhonov",
            "Tikhonet", "laplacian_kernel"]

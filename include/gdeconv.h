@@ -27,6 +27,9 @@
  *   gd_admm_iter_tail   the same, with the last two iterations' duals folded into one spectrum (256^2 Gaussian)
  *                       (X_Update :315-319, V_Update_{Poisson,Gaussian} :326-328/:335-336, duals
  *                       :212-213, next V step, output scaling :215)
+ *   gd_admm_train_init  models/Unrolled_ADMM.py:181-196 + init_l2 :170-175 and conv_fft_batch(H, x0) of :207, kept as images
+ *   gd_admm_train_iter  models/Unrolled_ADMM.py:199-215 loop body, out of place, saving what its adjoint needs
+ *   gd_admm_train_iter_backward  the adjoint of that body (autograd for training / fine-tuning Unrolled_ADMM)
  *   gd_wiener           models/Wiener.py:10-20       Wiener.forward(y, psf, alpha)
  *   gd_richardson_lucy  models/Richard_Lucy.py:10-24 Richard_Lucy(n_iters).forward(y, psf)
  *   gd_tikhonov         models/Tikhonet.py:15-31     Tikhonov(filter).forward(y, psf, alpha, lam)
@@ -47,7 +50,8 @@
 extern "C" {
 #endif
 
-#define GD_ABI_VERSION 5  /* 5: strict 0 / 1 fused-path setters, capture pipelining opt-in (mode 1 gone) */
+#define GD_ABI_VERSION 5  /* 5: strict 0 / 1 fused-path setters, capture pipelining opt-in (mode 1 gone);
+                             still 5, purely additive: gd_admm_train_saved_bytes / _init / _iter / _iter_backward */
 
 #define GD_OK 0
 #define GD_ERR_ARG (-1)
@@ -158,6 +162,51 @@ int gd_admm_iter_tail_v(const long long* argv);
 /* 1 exactly when gd_admm_iter would run k_gal_reg NOW for this call (Gaussian, 256^2, gd_set_fused_iteration on,
  * N >= gd_set_fused_min_batch(0, .)) and gd_set_combined_tail is on; else 0. */
 int gd_admm_tail_supported(int N, int H, int W, int llh);
+
+/* Training Unrolled_ADMM: the loop body as a differentiable, OUT-OF-PLACE function of images, and its adjoint.
+ * The state between denoiser calls is two images, u1 and w = v - u2 (u2' = H x' - w, so u2 and v are never needed
+ * apart).  With z = Z(zin) from the denoiser, D = rho1 |H|^2 + rho2:
+ *   X = (rho1 F(z - u1) + rho2 conj(H) F(w)) / D,  x = F^-1 X,  hx = F^-1(H X)          X_Update :315-319
+ *   not last:  u1' = u1 + x - z,  zin' = x + u1',  vt = 2 hx - w,  w' = V(vt; rho2_next) - (hx - w)   :207, :212-213
+ *   last:      out = x (times alpha for Poisson)                                                      :215
+ * V: V_Update_Poisson :326-328 / V_Update_Gaussian :335-336 (with y = max(y, 0); Gaussian: y / alpha).
+ *
+ * gd_admm_train_init: the OTF -> otf_half (gd_otf_bytes), x0 = clamp(init_l2) and hx0 = conv_fft_batch(H, x0); reads
+ *   no rho.  The caller forms zin_0 = x0, u1_0 = 0, w_0 = V(hx0; rho2[0]) (elementwise, once per forward).
+ * gd_admm_train_iter: one body.  y, z, u1, w are read-only; zin_or_out, u1_out, w_out (the latter two unused and
+ *   may be NULL when last != 0) and saved are written.  GD_ERR_ARG when an output is one of y, z, u1, w or two outputs
+ *   share a buffer (the graph's upstream nodes still hold the inputs).  saved: gd_admm_train_saved_bytes(N, H, W) =
+ *   1 x N (W/2+1) H 8 bytes, the half spectrum E = conj(H) F(w) - X, plus ONE image, N H W 4 bytes, vt (not written
+ *   when last).  E = D dX/drho2, and X is homogeneous of degree 0 in (rho1, rho2), so dX/drho1 = -(rho2 / rho1)
+ *   dX/drho2: neither X nor A = F(z - u1) is kept.
+ * gd_admm_train_iter_backward: given g_zin_or_out = dL/dzin' (last: dL/dout), g_u1_out = dL/du1', g_w_out = dL/dw'
+ *   (the latter two unused and may be NULL when last), the forward's y, scalars, OTF and saved, writes
+ *   g_z = dL/dz, g_u1 = dL/du1, g_w = dL/dw and g_rho_part, fp32 [N][2 (W/2+1) + H]: per galaxy (W/2+1) parts of
+ *   dL/drho1 (one per kx), (W/2+1) parts of dL/drho2, then H parts of dL/drho2_next (one per block of rows, the
+ *   block's other rows zero; all zero when last).  The caller sums each group per galaxy (and over galaxies for a
+ *   shared rho).  Three passes: a row-forward prologue (g_x = 2 g_zin + g_u1', g_vt = g_w' dV/dvt, g_hx = 2 g_vt - g_w',
+ *   the rho2_next parts), a column pass Q = (F(g_x) + conj(H) F(g_hx)) / D with the rho1 / rho2 parts
+ *   (1/HW) sum_k Re(conj(Q) E) (half-spectrum bins other than kx = 0, W/2 twice), a row-inverse epilogue
+ *   g_z = rho1 F^-1 Q - (g_zin + g_u1'), g_u1 = -g_z, g_w = g_w' - g_vt + rho2 F^-1(H Q).  No atomics: the same
+ *   inputs give bit-identical gradients.  Outputs must not alias inputs or each other (GD_ERR_ARG).
+ * No gradient flows to y, the PSF or alpha.  All three run the row / column chains whatever gd_set_fused_* and
+ * gd_set_fused_min_batch say, and honour gd_set_chunk_bytes / gd_set_pipeline_streams.  ws: gd_workspace_bytes.
+ * All validation precedes any HIP call. */
+size_t gd_admm_train_saved_bytes(int N, int H, int W);
+int gd_admm_train_init(const float* y, const float* psf, long long psf_gstride, int h, int w, const float* alpha,
+                       long long alpha_stride, int N, int H, int W, void* otf_half, float* x0, float* hx0, void* ws,
+                       void* stream);
+int gd_admm_train_iter(const float* y, const float* z, const float* u1, const float* w, const float* alpha,
+                       long long alpha_stride, const float* rho1, long long rho1_stride, const float* rho2,
+                       long long rho2_stride, const float* rho2_next, long long rho2_next_stride, int llh, int last,
+                       int N, int H, int W, const void* otf_half, float* zin_or_out, float* u1_out, float* w_out,
+                       void* saved, void* ws, void* stream);
+int gd_admm_train_iter_backward(const float* g_zin_or_out, const float* g_u1_out, const float* g_w_out, const float* y,
+                                const float* alpha, long long alpha_stride, const float* rho1, long long rho1_stride,
+                                const float* rho2, long long rho2_stride, const float* rho2_next,
+                                long long rho2_next_stride, int llh, int last, int N, int H, int W, const void* otf_half,
+                                const void* saved, float* g_z, float* g_u1, float* g_w, float* g_rho_part, void* ws,
+                                void* stream);
 
 /* x = Re IFFT2(conj(H) FFT2(y) / (|H|^2 + 350/alpha)). */
 int gd_wiener(const float* y, const float* psf, long long psf_gstride, int h, int w, const float* alpha,
