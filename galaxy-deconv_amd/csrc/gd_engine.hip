@@ -24,6 +24,10 @@
 //   ADMM loop body      models/Unrolled_ADMM.py:199-214 -> RF_ITER, C_ITER, RI_ITER
 //   the same, for training (out of place, saving conj(H) W - X and vt) -> RF_ITER, C_TRAIN, RI_TRAIN
 //   its adjoint (gd_admm_train_iter_backward)           -> RF_TRAIN_BWD, C_TRAIN_BWD, RI_TRAIN_BWD
+//   the same with gradients to y, the OTF and alpha (gd_admm_train_iter_full*) -> RF_ITER, C_TRAINF, RI_TRAINF and
+//                                                          RF_TRAINF_BWD, C_TRAINF_BWD, RI_TRAIN_BWD
+//   adjoint of psf_to_otf (gd_psf_to_otf_backward)      -> C_OTF_BWD, RI_PSF_BWD
+//   OTF gradient of conv_fft_batch (gd_conv_fft_batch_backward_otf) -> RF_TWO, C_XCORR
 //   Wiener.forward      models/Wiener.py:10-20          -> RF_PSF_RAW, C_WIENER, RI_OUT1
 //   Richard_Lucy.forward models/Richard_Lucy.py:10-24   -> RF_PSF_YP, C_OTF_CONV, RIF_RL_RATIO,
 //                                                          C_CONVC, RIF_RL_UPDATE / RI_RL_FINAL, C_CONV
@@ -97,17 +101,23 @@ struct Args {
     const float* a3;       // training body (gd_admm_train_*): the saved vt image (backward input)
     float* o3;             //   the vt image the forward saves
     float* part;           //   backward: d loss / d rho parts [N][2 K + H] (rho1 | rho2 per kx, rho2_next per row)
+    float* apart;          //   input-gradient backward (gd_admm_train_iter_full_backward): d loss / d alpha parts [N][H]
 };
 
 enum RowFwdMode { RF_ITER, RF_PSF_Y, RF_PSF_YP, RF_PSF_RAW, RF_PSF, RF_ONE, RF_TWO, RF_YA, RF_PSF_YAR,
                   RF_PADV, RF_PSF_YPAD, RF_PAD2,    // RF_PAD*: L/2 x L/2 sources zero-padded to L x L
-                  RF_TRAIN_BWD };                   // adjoint of the training body: g_x, g_hx from the incoming gradients
+                  RF_TRAIN_BWD,                     // adjoint of the training body: g_x, g_hx from the incoming gradients
+                  RF_TRAINF_BWD };                  // the same with input gradients: also g_y and the d/dalpha parts
 enum ColMode { C_ITER, C_OTF_INIT, C_OTF_CONV, C_WIENER, C_OTF, C_CONV, C_CONVC, C_CONV2, C_FWD, C_INV,
                C_G_INIT, C_G_ITER, C_G_W1, C_G_ITER_F, C_G_ITER_L, C_G_ITER_FL,  // _F first, _L last iteration
                C_TIKHONOV, C_POWER, C_GX_INIT, C_GX, C_GX_BWD,
-               C_TRAIN, C_TRAIN_BWD };  // C_ITER that saves conj(H) W - X for the backward; its adjoint
+               C_TRAIN, C_TRAIN_BWD,    // C_ITER that saves conj(H) W - X for the backward; its adjoint
+               C_OTF_BWD, C_XCORR,      // adjoint of C_OTF (gd_psf_to_otf_backward); cross spectrum (gd_conv_fft_batch_backward_otf)
+               C_TRAINF, C_TRAINF_BWD };  // C_TRAIN saving X and F(w) apart; its adjoint with the OTF gradient
 enum RowInvMode { RI_ITER, RI_INIT, RI_OUT1, RI_OUT2, RI_RL_FINAL, RI_CROP, RI_CROP_BWD,  // RI_CROP*: L/2 x L/2 sinks
-                  RI_TRAIN, RI_TRAIN_BWD };  // RI_ITER out of place (saves vt); the adjoint's sink
+                  RI_TRAIN, RI_TRAIN_BWD,    // RI_ITER out of place (saves vt); the adjoint's sink
+                  RI_PSF_BWD,                // adjoint of the PSF placement: the h x h window gathered back
+                  RI_TRAINF };               // RI_TRAIN that also keeps x when last (the alpha gradient of x alpha)
 enum RowInvFwdMode { RIF_CLAMP, RIF_RL_RATIO, RIF_RL_UPDATE };
 
 constexpr int rows_per_block(int lpb, int L) {
@@ -169,6 +179,24 @@ __device__ __forceinline__ void v_step_grad(int llh, float vt, float yp, float r
     const float q = 1.0f / (1.0f + rho2);
     dvt = rho2 * q;
     drho = (vt - yp / alpha) * q * q;
+}
+
+// d V / d yp and d V / d alpha at the same point (gd_admm_train_iter_full_backward).  Gaussian: 1 / (alpha (1 + rho2)) and
+// -yp / (alpha^2 (1 + rho2)).  Poisson: 1 / s and (1 - t / s) / (2 rho2) = (s - t) / (2 rho2 s), s - t formed without
+// cancellation as in v_step_grad.
+__device__ __forceinline__ void v_step_grad_in(int llh, float vt, float yp, float rho2, float alpha, float& dy,
+                                               float& dal) {
+    if (llh == GD_LLH_POISSON) {
+        const float t1 = rho2 * vt - alpha;
+        const float s = sqrtf(t1 * t1 + 4.0f * yp * rho2);
+        const float sm = t1 > 0.f ? 4.0f * yp * rho2 / (s + t1) : s - t1;  // s - t1
+        dy = 1.0f / s;
+        dal = 0.5f * sm / (rho2 * s);
+        return;
+    }
+    const float q = 1.0f / (alpha * (1.0f + rho2));
+    dy = q;
+    dal = -yp * q / alpha;
 }
 
 // ---------------------------------------------------------------- row-side building blocks
@@ -350,6 +378,51 @@ __device__ __forceinline__ float4 rf_train_bwd4(const Args& a, int g, int im, si
     return ghx;
 }
 
+// RF_TRAINF_BWD: rf_train_bwd4 with the input gradients of the V step (gd_admm_train_iter_full_backward).  o3 receives
+// g_y = g_w' dV/dyp where y > 0 (y+ = max(y, 0) passes no gradient at y <= 0; zero when last), acc2 collects this
+// thread's part of d loss / d alpha = sum g_w' dV/dalpha, and, on the last Poisson body, sum g_out x of the output
+// scaling x alpha (a3 then holds x, kept by RI_TRAINF in the vt slot).
+template <int L>
+__device__ __forceinline__ float4 rf_trainf_bwd4(const Args& a, int g, int im, size_t pix, float& acc, float& acc2) {
+    if (im == 0) {
+        const float4 gz = ld4(a.a0 + pix);
+        if (a.last) {
+            float sc = 1.f;
+            if (a.llh == GD_LLH_POISSON) {
+                const float4 x = ld4(a.a3 + pix);
+                sc = a.alpha(g);
+                acc2 += gz.x * x.x + gz.y * x.y + gz.z * x.z + gz.w * x.w;
+            }
+            return make_float4(gz.x * sc, gz.y * sc, gz.z * sc, gz.w * sc);
+        }
+        const float4 gu = ld4(a.a1 + pix);
+        return make_float4(2.f * gz.x + gu.x, 2.f * gz.y + gu.y, 2.f * gz.z + gu.z, 2.f * gz.w + gu.w);
+    }
+    if (a.last) {
+        st4(a.o3 + pix, make_float4(0.f, 0.f, 0.f, 0.f));
+        return make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    const float4 gw = ld4(a.a2 + pix), vt = ld4(a.a3 + pix), y = ld4(a.y + pix);
+    const float al = a.alpha(g), r2n = a.rho2n(g);
+    float4 ghx, wp, gy;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float dvt, drho, dy, dal;
+        const float ye = f4(y, e), yp = fmaxf(ye, 0.f);
+        v_step_grad(a.llh, f4(vt, e), yp, r2n, al, dvt, drho);
+        v_step_grad_in(a.llh, f4(vt, e), yp, r2n, al, dy, dal);
+        const float gwe = f4(gw, e), gvt = gwe * dvt;
+        acc += gwe * drho;
+        acc2 += gwe * dal;
+        f4set(ghx, e, 2.f * gvt - gwe);
+        f4set(wp, e, gwe - gvt);
+        f4set(gy, e, ye > 0.f ? gwe * dy : 0.f);
+    }
+    st4(a.o2 + pix, wp);
+    st4(a.o3 + pix, gy);
+    return ghx;
+}
+
 template <int L, int MODE, int RBX = 0>
 __global__ __launch_bounds__((RowGeo<L, RfTraits<MODE>::NI, RBX>::THREADS)) void k_row_fwd(Args a) {
     constexpr int NI = RfTraits<MODE>::NI;
@@ -367,15 +440,35 @@ __global__ __launch_bounds__((RowGeo<L, RfTraits<MODE>::NI, RBX>::THREADS)) void
     fill_twiddles<L>(tw, tid, R::THREADS);
     // stage the block's RB rows of each image through LDS with 16-byte coalesced loads
     float* stage = reinterpret_cast<float*>(lds);  // [im][rr][c]
-    [[maybe_unused]] float acc = 0.f;
+    [[maybe_unused]] float acc = 0.f, acc2 = 0.f;
     for (int q = tid * 4; q < NI * R::RB * L; q += R::THREADS * 4) {
         const int imq = q / (R::RB * L), rem = q - imq * (R::RB * L);
         const int rr = rem / L, c = rem - rr * L;
         const size_t pix = ((size_t)g * L + row0 + rr) * L + c;
         if constexpr (MODE == RF_TRAIN_BWD) st4(stage + q, rf_train_bwd4<L>(a, g, imq, pix, acc));
+        else if constexpr (MODE == RF_TRAINF_BWD) st4(stage + q, rf_trainf_bwd4<L>(a, g, imq, pix, acc, acc2));
         else st4(stage + q, rf_source4<L, MODE>(a, g, imq, row0 + rr, c, pix));
     }
-    if constexpr (MODE == RF_TRAIN_BWD) {
+    if constexpr (MODE == RF_TRAINF_BWD) {
+        // this block's part of d loss / d alpha -> apart[g][row0] (the block's other rows zero), in the fixed order
+        // of the rho2_next parts below
+        __shared__ float red2[R::THREADS];
+        red2[tid] = acc2;
+        __syncthreads();
+        if (tid < 64) {
+            float sum = 0.f;
+            for (int i = tid; i < R::THREADS; i += 64) sum += red2[i];
+            red2[tid] = sum;
+        }
+        __syncthreads();
+        if (tid < R::RB) {
+            float sum = 0.f;
+            if (tid == 0)
+                for (int i = 0; i < (R::THREADS < 64 ? R::THREADS : 64); ++i) sum += red2[i];
+            a.apart[(size_t)g * L + row0 + tid] = sum;
+        }
+    }
+    if constexpr (MODE == RF_TRAIN_BWD || MODE == RF_TRAINF_BWD) {
         // this block's part of d loss / d rho2_next, summed in a fixed order (no atomics: bit-identical reruns)
         // -> part[g][2 K + row0]; the block's other rows hold zero, so the caller sums all L entries
         __shared__ float red[R::THREADS];
@@ -468,13 +561,16 @@ template <int MODE>
 struct ColTraits {
     static constexpr bool IN2 = (MODE == C_ITER || MODE == C_OTF_INIT || MODE == C_OTF_CONV ||
                                  MODE == C_WIENER || MODE == C_CONV2 || MODE == C_TIKHONOV || MODE == C_GX_INIT ||
-                                 MODE == C_GX_BWD || MODE == C_TRAIN || MODE == C_TRAIN_BWD);
-    static constexpr bool OUT2 = (MODE == C_ITER || MODE == C_CONV2 || MODE == C_TRAIN || MODE == C_TRAIN_BWD);
-    static constexpr bool HAS_OUT = (MODE != C_OTF && MODE != C_FWD && MODE != C_G_W1 && MODE != C_POWER);
+                                 MODE == C_GX_BWD || MODE == C_TRAIN || MODE == C_TRAIN_BWD || MODE == C_XCORR ||
+                                 MODE == C_TRAINF || MODE == C_TRAINF_BWD);
+    static constexpr bool OUT2 = (MODE == C_ITER || MODE == C_CONV2 || MODE == C_TRAIN || MODE == C_TRAIN_BWD ||
+                                  MODE == C_TRAINF || MODE == C_TRAINF_BWD);
+    static constexpr bool HAS_OUT = (MODE != C_OTF && MODE != C_FWD && MODE != C_G_W1 && MODE != C_POWER &&
+                                     MODE != C_XCORR);
     static constexpr bool STORE_OTF = (MODE == C_OTF_INIT || MODE == C_OTF_CONV || MODE == C_OTF);
     static constexpr bool LOAD_OTF = (MODE == C_ITER || MODE == C_CONV || MODE == C_CONVC || MODE == C_CONV2 ||
-                                      MODE == C_TRAIN || MODE == C_TRAIN_BWD);
-    static constexpr bool FWD = (MODE != C_INV);
+                                      MODE == C_TRAIN || MODE == C_TRAIN_BWD || MODE == C_TRAINF || MODE == C_TRAINF_BWD);
+    static constexpr bool FWD = (MODE != C_INV && MODE != C_OTF_BWD);
 };
 
 // Gaussian ADMM iteration for one spectral element, entirely in the spectral domain (every step of
@@ -687,7 +783,8 @@ __global__ __launch_bounds__(256) void k_col(Args a) {
     const size_t c0 = tidx(g, 0, kx, 0, K, L), c1 = tidx(g, 1, kx, 0, K, L);
 #pragma unroll
     for (int s = 0; s < F2; ++s) {
-        P[s] = a.T[(MODE == C_G_W1 ? c1 : c0) + j + F1 * s];  // C_G_W1: x0's row spectra in slot 1
+        if constexpr (MODE == C_OTF_BWD) P[s] = a.otf[((size_t)g * K + kx) * L + j + F1 * s];  // the OTF gradient, not T
+        else P[s] = a.T[(MODE == C_G_W1 ? c1 : c0) + j + F1 * s];  // C_G_W1: x0's row spectra in slot 1
         if constexpr (TR::IN2) Q[s] = a.T[c1 + j + F1 * s];
     }
     __syncthreads();  // twiddles
@@ -718,7 +815,7 @@ __global__ __launch_bounds__(256) void k_col(Args a) {
     constexpr bool giter = (MODE == C_G_ITER || MODE == C_G_ITER_F || MODE == C_G_ITER_L || MODE == C_G_ITER_FL);
     constexpr bool gfirst = (MODE == C_G_ITER_F || MODE == C_G_ITER_FL);
     constexpr bool glast = (MODE == C_G_ITER_L || MODE == C_G_ITER_FL);
-    constexpr bool train = (MODE == C_TRAIN || MODE == C_TRAIN_BWD);
+    constexpr bool train = (MODE == C_TRAIN || MODE == C_TRAIN_BWD || MODE == C_TRAINF || MODE == C_TRAINF_BWD);
     const float r1 = (MODE == C_ITER || giter || train) ? a.rho1(g) : 0.f;
     const float r2 = (MODE == C_ITER || giter || train) ? a.rho2(g) : 0.f;
     const float r2n = (giter && !glast) ? a.rho2n(g) : 0.f;
@@ -731,7 +828,7 @@ __global__ __launch_bounds__(256) void k_col(Args a) {
         if constexpr (TR::STORE_OTF) {
             if (valid) a.otf[ob + ky] = Hk;
         }
-        if constexpr (MODE == C_ITER || MODE == C_TRAIN) {
+        if constexpr (MODE == C_ITER || MODE == C_TRAIN || MODE == C_TRAINF) {
             // runtime X_Update (models/Unrolled_ADMM.py:315-319):
             //   X = (rho1 F(z-u1) + rho2 conj(H) F(v-u2)) / (rho1 |H|^2 + rho2);  HX = H X
             const float HtH = Hk.x * Hk.x + Hk.y * Hk.y;
@@ -743,6 +840,13 @@ __global__ __launch_bounds__(256) void k_col(Args a) {
                 // kept for the backward: E = conj(H) W - X = lhs dX/drho2; dX/drho1 = -(rho2 / rho1) dX/drho2
                 // (X is homogeneous of degree 0 in (rho1, rho2)), so this one spectrum serves both
                 if (valid) a.s_w[ob + ky] = csub(HtW, X);
+            }
+            if constexpr (MODE == C_TRAINF) {
+                // input gradients (gd_admm_train_iter_full): the OTF gradient needs X and F(w) apart, so both are kept
+                if (valid) {
+                    a.s_w[ob + ky] = X;
+                    a.s_u1[ob + ky] = Q[s];
+                }
             }
             P[s] = cscale(X, inv_n);
             Q[s] = cscale(cmul(Hk, X), inv_n);
@@ -757,6 +861,26 @@ __global__ __launch_bounds__(256) void k_col(Args a) {
             const float2 E = a.s_w[ob + ky];
             const float wk = (kx == 0 || 2 * kx == L) ? 1.f : 2.f;
             drho += wk * (Qk.x * E.x + Qk.y * E.y);
+            P[s] = cscale(Qk, inv_n);
+            Q[s] = cscale(cmul(Hk, Qk), inv_n);
+        } else if constexpr (MODE == C_TRAINF_BWD) {
+            // C_TRAIN_BWD with the OTF gradient.  P = F(g_x), Q = F(g_hx), X and Wf = F(w) saved by C_TRAINF, E = conj(H)
+            // Wf - X re-formed.  With Qk = (F(g_x) + conj(H) F(g_hx)) / lhs, over the full spectrum
+            //   g_H = F(g_hx) conj(X) + rho2 conj(Qk) Wf - 2 rho1 H Re(Qk conj(X)),
+            // stored as (wk / L^2) g_H: the mirrored bins folded into the stored one (gdeconv.h's convention)
+            const float HtH = Hk.x * Hk.x + Hk.y * Hk.y;
+            const float lhs = r1 * HtH + r2;
+            const float2 Ghx = Q[s];
+            const float2 HtG = cmulc(Ghx, Hk);
+            const float2 Qk = make_float2((P[s].x + HtG.x) / lhs, (P[s].y + HtG.y) / lhs);
+            const float2 X = a.s_w[ob + ky], Wf = a.s_u1[ob + ky];
+            const float2 E = csub(cmulc(Wf, Hk), X);
+            const float wk = (kx == 0 || 2 * kx == L) ? 1.f : 2.f;
+            drho += wk * (Qk.x * E.x + Qk.y * E.y);
+            const float2 t1 = cmulc(Ghx, X), t2 = cmulc(Wf, Qk);
+            const float re = 2.f * r1 * (Qk.x * X.x + Qk.y * X.y);
+            if (valid)
+                a.s_g[ob + ky] = cscale(make_float2(t1.x + r2 * t2.x - re * Hk.x, t1.y + r2 * t2.y - re * Hk.y), wk * inv_n);
             P[s] = cscale(Qk, inv_n);
             Q[s] = cscale(cmul(Hk, Qk), inv_n);
         } else if constexpr (MODE == C_OTF_INIT) {
@@ -844,6 +968,16 @@ __global__ __launch_bounds__(256) void k_col(Args a) {
             Q[s] = cscale(cmul(Q[s], Hk), inv_n);
         } else if constexpr (MODE == C_INV) {
             P[s] = cscale(P[s], inv_n);
+        } else if constexpr (MODE == C_OTF_BWD) {
+            // transpose of the forward transform under dL = sum over the STORED bins of Re(conj(G) dOTF): the row
+            // inverse's Hermitian extension counts every column but kx = 0, L/2 twice, so those are halved here;
+            // unnormalised (the forward transform is)
+            P[s] = cscale(P[s], (kx == 0 || 2 * kx == L) ? 1.f : 0.5f);
+        } else if constexpr (MODE == C_XCORR) {
+            // OTF gradient of out = F^-1(H F x) (a.last: conj(H)): F(g_out) conj(F x) / L^2 (conjugated), the mirrored
+            // bins folded into the stored one (every column but kx = 0, L/2 twice)
+            const float wk = ((kx == 0 || 2 * kx == L) ? 1.f : 2.f) * inv_n;
+            if (valid) a.otf[ob + ky] = cscale(a.last ? cmulc(Q[s], P[s]) : cmulc(P[s], Q[s]), wk);
         }
     }
     if constexpr (MODE == C_GX_BWD) {
@@ -851,7 +985,7 @@ __global__ __launch_bounds__(256) void k_col(Args a) {
         for (int off = F1 / 2; off > 0; off >>= 1) drho += __shfl_xor(drho, off, F1);
         if (valid && j == 0) a.o2[(size_t)g * K + kx] = drho * inv_n;
     }
-    if constexpr (MODE == C_TRAIN_BWD) {
+    if constexpr (MODE == C_TRAIN_BWD || MODE == C_TRAINF_BWD) {
 #pragma unroll
         for (int off = F1 / 2; off > 0; off >>= 1) drho += __shfl_xor(drho, off, F1);
         if (valid && j == 0) {
@@ -2055,7 +2189,8 @@ __global__ __launch_bounds__(subnet::kThreads, GD_SN_WPE) void k_subnet_rhos_ini
 // ---------------------------------------------------------------- RI: row inverse + sink
 template <int MODE>
 struct RiTraits {
-    static constexpr int NI = (MODE == RI_ITER || MODE == RI_OUT2 || MODE == RI_TRAIN || MODE == RI_TRAIN_BWD) ? 2 : 1;
+    static constexpr int NI = (MODE == RI_ITER || MODE == RI_OUT2 || MODE == RI_TRAIN || MODE == RI_TRAIN_BWD ||
+                               MODE == RI_TRAINF) ? 2 : 1;
 };
 
 template <int L, int MODE, int RBX = 0>
@@ -2091,9 +2226,9 @@ __global__ __launch_bounds__((RowGeo<L, RiTraits<MODE>::NI, RBX>::THREADS)) void
     __syncthreads();
 
     float al = 1.f, r2n = 1.f, div = 1.f;
-    if constexpr (MODE == RI_ITER || MODE == RI_INIT || MODE == RI_TRAIN) {
+    if constexpr (MODE == RI_ITER || MODE == RI_INIT || MODE == RI_TRAIN || MODE == RI_TRAINF) {
         al = a.alpha(g);
-        if (!((MODE == RI_ITER || MODE == RI_TRAIN) && a.last)) r2n = a.rho2n(g);
+        if (!((MODE == RI_ITER || MODE == RI_TRAIN || MODE == RI_TRAINF) && a.last)) r2n = a.rho2n(g);
     }
     if constexpr (MODE == RI_RL_FINAL) div = a.otf[(size_t)g * G::K * L].x;  // conv(Ht, ones) = H(0,0)
     if constexpr (MODE == RI_CROP || MODE == RI_CROP_BWD) {
@@ -2115,6 +2250,19 @@ __global__ __launch_bounds__((RowGeo<L, RiTraits<MODE>::NI, RBX>::THREADS)) void
                 st4(a.o0 + p, make_float4(rho * X.x, rho * X.y, rho * X.z, rho * X.w));
                 st4(a.o1 + p, make_float4(-X.x, -X.y, -X.z, -X.w));
             }
+        }
+        return;
+    }
+    if constexpr (MODE == RI_PSF_BWD) {
+        // adjoint of shifted_psf: image pixel (r, c) is psf pixel ((r + h/2) mod L, (c + h/2) mod L) when both are
+        // < h; every psf pixel has exactly one source, so o0 [N][h][h] is written once, in bounds by the test
+        const int h = a.h, c0 = h >> 1;
+        for (int q = tid; q < R::RB * L; q += R::THREADS) {
+            const int rr = q / L, c = q - rr * L;
+            int i = row0 + rr + c0, jj = c + c0;
+            if (i >= L) i -= L;
+            if (jj >= L) jj -= L;
+            if (i < h && jj < h) a.o0[((size_t)g * h + i) * h + jj] = res[rr * L + c];
         }
         return;
     }
@@ -2148,7 +2296,7 @@ __global__ __launch_bounds__((RowGeo<L, RiTraits<MODE>::NI, RBX>::THREADS)) void
                 st4(a.o1 + pix, wo);
                 st4(a.o2 + pix, zo);
             }
-        } else if constexpr (MODE == RI_TRAIN) {
+        } else if constexpr (MODE == RI_TRAIN || MODE == RI_TRAINF) {
             // RI_ITER out of place (gd_admm_train_iter): u1 (a1) and w (a2) are read-only, u1' -> o0, w' -> o1,
             // zin' -> o2, and vt = 2 hx - w, the V step's argument, -> o3 for the backward
             const float4 HX = ld4(res + (R::RB + rr) * L + c);
@@ -2156,6 +2304,7 @@ __global__ __launch_bounds__((RowGeo<L, RiTraits<MODE>::NI, RBX>::THREADS)) void
                 float4 o = X;
                 if (poisson) o = make_float4(X.x * al, X.y * al, X.z * al, X.w * al);
                 st4(a.o2 + pix, o);
+                if constexpr (MODE == RI_TRAINF) st4(a.o3 + pix, X);  // x in the (otherwise unused) vt slot: d(x alpha)/dalpha
             } else {
                 const float4 Z = ld4(a.a0 + pix), U1 = ld4(a.a1 + pix), Wv = ld4(a.a2 + pix), Y = ld4(a.y + pix);
                 float4 u1o, wo, zo, vto;
@@ -2611,6 +2760,7 @@ inline Args offset_args(const Args& a, int g0, int n, int H, int W) {
     if (b.a3) b.a3 += img;
     if (b.o3) b.o3 += img;
     if (b.part) b.part += (size_t)g0 * (2 * (W / 2 + 1) + H);
+    if (b.apart) b.apart += (size_t)g0 * H;
     if (b.psf) b.psf += (long long)g0 * a.psf_gstride;
     GalScalar* gs[] = {&b.alpha, &b.rho1, &b.rho2, &b.rho2n};
     for (GalScalar* x : gs)
@@ -2753,6 +2903,16 @@ struct Ops {
         GD_TRY(Lc::template col<C_INV>(a, st));
         return Lc::template ri<RI_OUT1>(a, st);
     }
+    // Adjoints for input gradients: a.otf = the OTF gradient (read), a.o0 <- g_psf [N][h][h]
+    static int psf_to_otf_bwd(Args a, hipStream_t st) {
+        GD_TRY(Lc::template col<C_OTF_BWD>(a, st));
+        return Lc::template ri<RI_PSF_BWD>(a, st);
+    }
+    // a.a0 = g_out, a.a1 = x, a.last = conj; a.otf <- the OTF gradient
+    static int conv_bwd_otf(Args a, hipStream_t st) {
+        GD_TRY(Lc::template rf<RF_TWO>(a, st));
+        return Lc::template col<C_XCORR>(a, st);
+    }
     // Poisson in two whole-galaxy passes per iteration at 256^2 (gd_poisreg.hpp): the Gaussian init's
     // |H|^2, x0 -> zin and F(x0) with the OTF in the G slot, then pass B with u2 = 0 (w1, W~1)
     static int admm_init_pois2(Args a0, hipStream_t st0) {
@@ -2876,6 +3036,21 @@ struct Ops {
         return for_chunks(a0, L, st0, [&](const Args& a, hipStream_t st) {
             GD_TRY(Lc::template rf<RF_TRAIN_BWD>(a, st));
             GD_TRY(Lc::template col<C_TRAIN_BWD>(a, st));
+            return Lc::template ri<RI_TRAIN_BWD>(a, st);
+        });
+    }
+    // The same body and adjoint with input gradients (gd_admm_train_iter_full*)
+    static int train_iter_full(Args a0, hipStream_t st0) {
+        return for_chunks(a0, L, st0, [&](const Args& a, hipStream_t st) {
+            GD_TRY(Lc::template rf<RF_ITER>(a, st));
+            GD_TRY(Lc::template col<C_TRAINF>(a, st));
+            return Lc::template ri<RI_TRAINF>(a, st);
+        });
+    }
+    static int train_iter_full_bwd(Args a0, hipStream_t st0) {
+        return for_chunks(a0, L, st0, [&](const Args& a, hipStream_t st) {
+            GD_TRY(Lc::template rf<RF_TRAINF_BWD>(a, st));
+            GD_TRY(Lc::template col<C_TRAINF_BWD>(a, st));
             return Lc::template ri<RI_TRAIN_BWD>(a, st);
         });
     }
@@ -3063,7 +3238,7 @@ int gd_abi_version(void) { return GD_ABI_VERSION; }
 
 // bumped whenever a kernel's memory traffic changes; PMC summaries are stamped with it so a stale
 // profile is never reported against a different engine
-const char* gd_engine_rev(void) { return "r08.0"; }
+const char* gd_engine_rev(void) { return "r09.0"; }
 
 // the source hash __graft_entry__.build() computed (gdeconv._lib.source_hash); the "gdsrc:" marker lets the
 // build find it in the binary without loading it
@@ -3140,6 +3315,36 @@ int gd_irfft2(void* spec, float* x, int N, int H, int W, void* stream) {
     Args a = base_args(N, spec, H, W);
     a.o0 = x;
     return dispatch<Ops>(H, W, [&](auto op) { return decltype(op)::irfft2(a, (hipStream_t)stream); });
+}
+
+// ---------------------------------------------------------------- input gradients: the OTF-gradient producers' adjoints
+int gd_psf_to_otf_backward(const void* g_otf_half, int h, int w, int N, int H, int W, float* g_psf, void* ws,
+                           void* stream) {
+    GD_TRY(check_shape(N, H, W));
+    GD_TRY(check_psf(h, w, H, W));
+    if (N == 0) return GD_OK;
+    if (!g_otf_half || !g_psf || !ws) return fail(GD_ERR_ARG, "gd_psf_to_otf_backward: null pointer");
+    if ((const void*)g_psf == g_otf_half || (void*)g_psf == ws || g_otf_half == ws)
+        return fail(GD_ERR_ARG, "gd_psf_to_otf_backward: g_psf, g_otf_half and ws must be distinct buffers");
+    Args a = base_args(N, ws, H, W);
+    a.h = h;
+    a.otf = reinterpret_cast<float2*>(const_cast<void*>(g_otf_half));
+    a.o0 = g_psf;
+    return dispatch<Ops>(H, W, [&](auto op) { return decltype(op)::psf_to_otf_bwd(a, (hipStream_t)stream); });
+}
+
+int gd_conv_fft_batch_backward_otf(const float* x, const float* g_out, int conj, int N, int H, int W, void* g_otf_half,
+                                   void* ws, void* stream) {
+    GD_TRY(check_shape(N, H, W));
+    if (N == 0) return GD_OK;
+    if (!x || !g_out || !g_otf_half || !ws) return fail(GD_ERR_ARG, "gd_conv_fft_batch_backward_otf: null pointer");
+    if (g_otf_half == (const void*)x || g_otf_half == (const void*)g_out || g_otf_half == ws)
+        return fail(GD_ERR_ARG, "gd_conv_fft_batch_backward_otf: g_otf_half aliases an input or the workspace");
+    Args a = base_args(N, ws, H, W);
+    a.a0 = g_out; a.a1 = x;
+    a.last = conj != 0;
+    a.otf = reinterpret_cast<float2*>(g_otf_half);
+    return dispatch<Ops>(H, W, [&](auto op) { return decltype(op)::conv_bwd_otf(a, (hipStream_t)stream); });
 }
 
 // Gap between the Gaussian state's slots at 256^2 (bytes).  The slots are N K L complex apart, a multiple of 8 MiB
@@ -3419,6 +3624,100 @@ int gd_admm_train_iter_backward(const float* g_zin_or_out, const float* g_u1_out
     a.part = g_rho_part;
     ProfScope ps("op_admm_train_bwd<" + std::to_string(H) + "," + std::to_string(llh) + ">", (hipStream_t)stream, 1);
     return dispatch<Ops>(H, W, [&](auto op) { return decltype(op)::train_iter_bwd(a, (hipStream_t)stream); });
+}
+
+// ---------------------------------------------------------------- training with input gradients (y, the OTF, alpha)
+// saved per iteration: [X | F(w), two half spectra N K H complex each | vt = 2 H x - w (last: x), image N H W floats]
+size_t gd_admm_train_full_saved_bytes(int N, int H, int W) {
+    if (!gd_supported_size(H, W) || N <= 0) return 0;
+    return 2 * (size_t)N * (W / 2 + 1) * H * sizeof(float2) + (size_t)N * H * W * sizeof(float);
+}
+
+int gd_admm_train_iter_full(const float* y, const float* z, const float* u1, const float* w, const float* alpha,
+                            long long alpha_stride, const float* rho1, long long rho1_stride, const float* rho2,
+                            long long rho2_stride, const float* rho2_next, long long rho2_next_stride, int llh, int last,
+                            int N, int H, int W, const void* otf_half, float* zin_or_out, float* u1_out, float* w_out,
+                            void* saved, void* ws, void* stream) {
+    GD_TRY(check_shape(N, H, W));
+    if (llh != GD_LLH_GAUSSIAN && llh != GD_LLH_POISSON) return fail(GD_ERR_ARG, "llh must be Gaussian or Poisson");
+    if (!y || !z || !u1 || !w || !alpha || !rho1 || !rho2 || !otf_half || !zin_or_out || !saved || !ws)
+        return fail(GD_ERR_ARG, "gd_admm_train_iter_full: null pointer");
+    if (!last && (!rho2_next || !u1_out || !w_out))
+        return fail(GD_ERR_ARG, "gd_admm_train_iter_full: rho2_next, u1_out and w_out required unless last");
+    {
+        const void* in[] = {y, z, u1, w, otf_half};
+        const void* out[] = {zin_or_out, last ? nullptr : u1_out, last ? nullptr : w_out, saved};
+        for (int i = 0; i < 4; ++i) {
+            if (!out[i]) continue;
+            for (const void* p : in)
+                if (out[i] == p) return fail(GD_ERR_ARG, "gd_admm_train_iter_full: an output aliases an input (the body is out of place)");
+            for (int k = 0; k < i; ++k)
+                if (out[i] == out[k]) return fail(GD_ERR_ARG, "gd_admm_train_iter_full: two outputs share a buffer");
+        }
+    }
+    if (N == 0) return GD_OK;
+    const size_t spec = (size_t)N * (W / 2 + 1) * H;
+    Args a = base_args(N, ws, H, W);
+    a.y = y; a.a0 = z; a.a1 = u1; a.a2 = w;
+    a.alpha = GalScalar{alpha, alpha_stride};
+    a.rho1 = GalScalar{rho1, rho1_stride};
+    a.rho2 = GalScalar{rho2, rho2_stride};
+    a.rho2n = GalScalar{rho2_next ? rho2_next : rho2, rho2_next ? rho2_next_stride : rho2_stride};
+    a.llh = llh;
+    a.last = last != 0;
+    a.otf = reinterpret_cast<float2*>(const_cast<void*>(otf_half));
+    a.o0 = u1_out; a.o1 = w_out; a.o2 = zin_or_out;
+    a.s_w = reinterpret_cast<float2*>(saved);   // X
+    a.s_u1 = a.s_w + spec;                      // F(w)
+    a.o3 = reinterpret_cast<float*>(a.s_u1 + spec);
+    ProfScope ps("op_admm_train_iter_full<" + std::to_string(H) + "," + std::to_string(llh) + ">", (hipStream_t)stream, 1);
+    return dispatch<Ops>(H, W, [&](auto op) { return decltype(op)::train_iter_full(a, (hipStream_t)stream); });
+}
+
+int gd_admm_train_iter_full_backward(const float* g_zin_or_out, const float* g_u1_out, const float* g_w_out,
+                                     const float* y, const float* alpha, long long alpha_stride, const float* rho1,
+                                     long long rho1_stride, const float* rho2, long long rho2_stride,
+                                     const float* rho2_next, long long rho2_next_stride, int llh, int last, int N, int H,
+                                     int W, const void* otf_half, const void* saved, float* g_z, float* g_u1, float* g_w,
+                                     float* g_rho_part, void* g_otf_half, float* g_y, float* g_alpha_part, void* ws,
+                                     void* stream) {
+    GD_TRY(check_shape(N, H, W));
+    if (llh != GD_LLH_GAUSSIAN && llh != GD_LLH_POISSON) return fail(GD_ERR_ARG, "llh must be Gaussian or Poisson");
+    if (!g_zin_or_out || !y || !alpha || !rho1 || !rho2 || !otf_half || !saved || !g_z || !g_u1 || !g_w || !g_rho_part ||
+        !g_otf_half || !g_y || !g_alpha_part || !ws)
+        return fail(GD_ERR_ARG, "gd_admm_train_iter_full_backward: null pointer");
+    if (!last && (!rho2_next || !g_u1_out || !g_w_out))
+        return fail(GD_ERR_ARG, "gd_admm_train_iter_full_backward: rho2_next, g_u1_out and g_w_out required unless last");
+    {
+        const void* in[] = {g_zin_or_out, g_u1_out, g_w_out, y, saved, otf_half};
+        const void* out[] = {g_z, g_u1, g_w, g_rho_part, g_otf_half, g_y, g_alpha_part};
+        for (int i = 0; i < 7; ++i) {
+            for (const void* p : in)
+                if (out[i] == p) return fail(GD_ERR_ARG, "gd_admm_train_iter_full_backward: an output aliases an input");
+            for (int k = 0; k < i; ++k)
+                if (out[i] == out[k]) return fail(GD_ERR_ARG, "gd_admm_train_iter_full_backward: two outputs share a buffer");
+        }
+    }
+    if (N == 0) return GD_OK;
+    const size_t spec = (size_t)N * (W / 2 + 1) * H;
+    Args a = base_args(N, ws, H, W);
+    a.y = y; a.a0 = g_zin_or_out; a.a1 = g_u1_out; a.a2 = g_w_out;
+    a.alpha = GalScalar{alpha, alpha_stride};
+    a.rho1 = GalScalar{rho1, rho1_stride};
+    a.rho2 = GalScalar{rho2, rho2_stride};
+    a.rho2n = GalScalar{rho2_next ? rho2_next : rho2, rho2_next ? rho2_next_stride : rho2_stride};
+    a.llh = llh;
+    a.last = last != 0;
+    a.otf = reinterpret_cast<float2*>(const_cast<void*>(otf_half));
+    a.s_w = reinterpret_cast<float2*>(const_cast<void*>(saved));
+    a.s_u1 = a.s_w + spec;
+    a.a3 = reinterpret_cast<const float*>(a.s_u1 + spec);
+    a.s_g = reinterpret_cast<float2*>(g_otf_half);
+    a.o0 = g_z; a.o1 = g_u1; a.o2 = g_w; a.o3 = g_y;
+    a.part = g_rho_part;
+    a.apart = g_alpha_part;
+    ProfScope ps("op_admm_train_full_bwd<" + std::to_string(H) + "," + std::to_string(llh) + ">", (hipStream_t)stream, 1);
+    return dispatch<Ops>(H, W, [&](auto op) { return decltype(op)::train_iter_full_bwd(a, (hipStream_t)stream); });
 }
 
 int gd_wiener(const float* y, const float* psf, long long psf_gstride, int h, int w, const float* alpha,

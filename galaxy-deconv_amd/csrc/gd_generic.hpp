@@ -304,6 +304,34 @@ __device__ __forceinline__ float gsrc_train_bwd(const Args& a, const Dims& d, in
     return 2.f * gvt - gw;      // g_hx
 }
 
+// RF_TRAINF_BWD's producer (gd_engine.hip rf_trainf_bwd4): gsrc_train_bwd plus g_y -> o3 and the d/dalpha terms
+__device__ __forceinline__ float gsrc_trainf_bwd(const Args& a, const Dims& d, int g, int im, int r, int c, float& acc,
+                                                 float& acc2) {
+    const size_t pix = ((size_t)g * d.H + r) * d.W + c;
+    if (im == 0) {
+        if (a.last) {
+            if (a.llh != GD_LLH_POISSON) return a.a0[pix];
+            acc2 += a.a0[pix] * a.a3[pix];                 // g_out x: the output scaling x alpha (a3 = x when last)
+            return a.a0[pix] * a.alpha(g);
+        }
+        return 2.f * a.a0[pix] + a.a1[pix];
+    }
+    if (a.last) {
+        a.o3[pix] = 0.f;
+        return 0.f;
+    }
+    float dvt, drho, dy, dal;
+    const float ye = a.y[pix], yp = fmaxf(ye, 0.f);
+    v_step_grad(a.llh, a.a3[pix], yp, a.rho2n(g), a.alpha(g), dvt, drho);
+    v_step_grad_in(a.llh, a.a3[pix], yp, a.rho2n(g), a.alpha(g), dy, dal);
+    const float gw = a.a2[pix], gvt = gw * dvt;
+    acc += gw * drho;
+    acc2 += gw * dal;
+    a.o2[pix] = gw - gvt;
+    a.o3[pix] = ye > 0.f ? gw * dy : 0.f;                  // g_y: y+ = max(y, 0) passes gradient where y > 0
+    return 2.f * gvt - gw;
+}
+
 // rows 2 pr, 2 pr + 1 of image im (pr = p0 + mm) -> line im pb + mm; the spectra of each image's rows
 // from the packed line spectra C: row 2m (C + conj D)/2, row 2m+1 (C - conj D)/(2i), D = C[(W - k) mod W]
 __device__ __forceinline__ void gsplit_store(const Args& a, const Dims& d, const float2* res, int g, int p0, int pb,
@@ -357,7 +385,7 @@ __global__ __launch_bounds__(kThreads) void k_gen_rf(Args a, Dims d) {
     float2* x = gsm + W;
     float2* y = x + nl * W;
     fill_tw(tw, W);
-    [[maybe_unused]] float acc = 0.f;
+    [[maybe_unused]] float acc = 0.f, acc2 = 0.f;
     for (int e = threadIdx.x; e < nl * W; e += blockDim.x) {
         const int line = e / W, c = e - line * W;
         const int im = line / pb, r0 = 2 * (p0 + line - im * pb);
@@ -365,13 +393,31 @@ __global__ __launch_bounds__(kThreads) void k_gen_rf(Args a, Dims d) {
         if constexpr (MODE == RF_TRAIN_BWD) {
             if (r0 < H) v0 = gsrc_train_bwd(a, d, g, im, r0, c, acc);
             if (r0 + 1 < H) v1 = gsrc_train_bwd(a, d, g, im, r0 + 1, c, acc);
+        } else if constexpr (MODE == RF_TRAINF_BWD) {
+            if (r0 < H) v0 = gsrc_trainf_bwd(a, d, g, im, r0, c, acc, acc2);
+            if (r0 + 1 < H) v1 = gsrc_trainf_bwd(a, d, g, im, r0 + 1, c, acc, acc2);
         } else {
             if (r0 < H) v0 = gsrc<MODE>(a, d, g, im, r0, c);
             if (r0 + 1 < H) v1 = gsrc<MODE>(a, d, g, im, r0 + 1, c);
         }
         x[e] = make_float2(v0, v1);
     }
-    if constexpr (MODE == RF_TRAIN_BWD) {
+    if constexpr (MODE == RF_TRAINF_BWD) {
+        // this block's part of d loss / d alpha -> apart[g][first row], its other rows zero (as the rho2_next parts
+        // below; the wave sums sit behind theirs in the second line buffer)
+        float* red2 = reinterpret_cast<float*>(y) + kThreads / 64;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc2 += __shfl_xor(acc2, off);
+        if ((threadIdx.x & 63) == 0) red2[threadIdx.x >> 6] = acc2;
+        __syncthreads();
+        for (int rr = threadIdx.x; rr < 2 * pb && 2 * p0 + rr < H; rr += blockDim.x) {
+            float sum = 0.f;
+            if (rr == 0)
+                for (int i = 0; i < kThreads / 64; ++i) sum += red2[i];
+            a.apart[(size_t)g * H + 2 * p0 + rr] = sum;
+        }
+    }
+    if constexpr (MODE == RF_TRAIN_BWD || MODE == RF_TRAINF_BWD) {
         // this block's part of d loss / d rho2_next in a fixed order -> part[g][2 K + first row]; its other rows zero
         // (kThreads = 4 full waves; the wave sums pass through the still unused second line buffer: no static LDS
         // next to a dynamic allocation that may fill the 64 KiB)
@@ -418,7 +464,8 @@ __global__ __launch_bounds__(kThreads) void k_gen_col(Args a, Dims d) {
         float2 v = make_float2(0.f, 0.f);
         if (f < NK) {
             const int g = f / K, kx = f - g * K;
-            v = a.T[tidx(g, MODE == C_G_W1 ? 1 : im, kx, ky, K, H)];  // C_G_W1: x0's row spectra in slot 1
+            if constexpr (MODE == C_OTF_BWD) v = a.otf[((size_t)g * K + kx) * H + ky];  // the OTF gradient, not T
+            else v = a.T[tidx(g, MODE == C_G_W1 ? 1 : im, kx, ky, K, H)];  // C_G_W1: x0's row spectra in slot 1
         }
         x[e] = v;
     }
@@ -433,7 +480,7 @@ __global__ __launch_bounds__(kThreads) void k_gen_col(Args a, Dims d) {
     for (int e = threadIdx.x; e < cb * H; e += blockDim.x) {
         const int cc = e / H, ky = e - cc * H, f = f0 + cc;
         if (f >= NK) {
-            if constexpr (MODE == C_GX_BWD || MODE == C_TRAIN_BWD) part[e] = 0.f;
+            if constexpr (MODE == C_GX_BWD || MODE == C_TRAIN_BWD || MODE == C_TRAINF_BWD) part[e] = 0.f;
             continue;
         }
         const int g = f / K, kx = f - g * K;
@@ -445,7 +492,7 @@ __global__ __launch_bounds__(kThreads) void k_gen_col(Args a, Dims d) {
         if constexpr (TR::LOAD_OTF) Hk = a.otf[(a.otf_bcast ? (size_t)kx * H : ob) + ky];
         if constexpr (TR::STORE_OTF || MODE == C_WIENER || MODE == C_TIKHONOV) Hk = Pv;
         if constexpr (TR::STORE_OTF) a.otf[o] = Hk;
-        if constexpr (MODE == C_ITER || MODE == C_TRAIN) {
+        if constexpr (MODE == C_ITER || MODE == C_TRAIN || MODE == C_TRAINF) {
             // runtime X_Update (models/Unrolled_ADMM.py:315-319): X = (rho1 F(z-u1) + rho2 conj(H) F(w)) / lhs
             const float r1 = a.rho1(g), r2 = a.rho2(g);
             const float HtH = Hk.x * Hk.x + Hk.y * Hk.y;
@@ -454,6 +501,10 @@ __global__ __launch_bounds__(kThreads) void k_gen_col(Args a, Dims d) {
             const float2 rhs = make_float2(r1 * Pv.x + r2 * HtW.x, r1 * Pv.y + r2 * HtW.y);
             const float2 X = make_float2(rhs.x / lhs, rhs.y / lhs);
             if constexpr (MODE == C_TRAIN) a.s_w[o] = csub(HtW, X);  // E = conj(H) W - X, kept for the backward
+            if constexpr (MODE == C_TRAINF) {                         // input gradients: X and F(w) kept apart
+                a.s_w[o] = X;
+                a.s_u1[o] = Qv;
+            }
             Pv = cscale(X, inv_n);
             P[(cb + cc) * H + ky] = cscale(cmul(Hk, X), inv_n);
         } else if constexpr (MODE == C_TRAIN_BWD) {
@@ -466,6 +517,22 @@ __global__ __launch_bounds__(kThreads) void k_gen_col(Args a, Dims d) {
             const float2 E = a.s_w[o];
             const float wk = (kx == 0 || 2 * kx == W) ? 1.f : 2.f;
             part[e] = wk * (Qk.x * E.x + Qk.y * E.y);
+            Pv = cscale(Qk, inv_n);
+            P[(cb + cc) * H + ky] = cscale(cmul(Hk, Qk), inv_n);
+        } else if constexpr (MODE == C_TRAINF_BWD) {
+            // C_TRAIN_BWD with the OTF gradient (gd_engine.hip C_TRAINF_BWD): X and Wf = F(w) saved apart
+            const float r1 = a.rho1(g), r2 = a.rho2(g);
+            const float HtH = Hk.x * Hk.x + Hk.y * Hk.y;
+            const float lhs = r1 * HtH + r2;
+            const float2 HtG = cmulc(Qv, Hk);
+            const float2 Qk = make_float2((Pv.x + HtG.x) / lhs, (Pv.y + HtG.y) / lhs);
+            const float2 X = a.s_w[o], Wf = a.s_u1[o];
+            const float2 E = csub(cmulc(Wf, Hk), X);
+            const float wk = (kx == 0 || 2 * kx == W) ? 1.f : 2.f;
+            part[e] = wk * (Qk.x * E.x + Qk.y * E.y);
+            const float2 t1 = cmulc(Qv, X), t2 = cmulc(Wf, Qk);
+            const float re = 2.f * r1 * (Qk.x * X.x + Qk.y * X.y);
+            a.s_g[o] = cscale(make_float2(t1.x + r2 * t2.x - re * Hk.x, t1.y + r2 * t2.y - re * Hk.y), wk * inv_n);
             Pv = cscale(Qk, inv_n);
             P[(cb + cc) * H + ky] = cscale(cmul(Hk, Qk), inv_n);
         } else if constexpr (MODE == C_OTF_INIT) {
@@ -550,6 +617,13 @@ __global__ __launch_bounds__(kThreads) void k_gen_col(Args a, Dims d) {
             P[(cb + cc) * H + ky] = cscale(cmul(Qv, Hk), inv_n);
         } else if constexpr (MODE == C_INV) {
             Pv = cscale(Pv, inv_n);
+        } else if constexpr (MODE == C_OTF_BWD) {
+            // transpose of the forward transform over the stored bins (gd_engine.hip C_OTF_BWD); unnormalised
+            Pv = cscale(Pv, (kx == 0 || 2 * kx == W) ? 1.f : 0.5f);
+        } else if constexpr (MODE == C_XCORR) {
+            // OTF gradient of the convolution (gd_engine.hip C_XCORR): F(g_out) conj(F x) / (H W), mirrored bins folded
+            const float wk = ((kx == 0 || 2 * kx == W) ? 1.f : 2.f) * inv_n;
+            a.otf[o] = cscale(a.last ? cmulc(Qv, Pv) : cmulc(Pv, Qv), wk);
         }
     }
     __syncthreads();
@@ -562,7 +636,7 @@ __global__ __launch_bounds__(kThreads) void k_gen_col(Args a, Dims d) {
         }
         __syncthreads();
     }
-    if constexpr (MODE == C_TRAIN_BWD) {
+    if constexpr (MODE == C_TRAIN_BWD || MODE == C_TRAINF_BWD) {
         if ((int)threadIdx.x < cb && f0 + (int)threadIdx.x < NK) {  // fixed-order sum per column
             const int f = f0 + threadIdx.x, g = f / K, kx = f - g * K;
             float s = 0.f;
@@ -606,9 +680,9 @@ __global__ __launch_bounds__(kThreads) void k_gen_ri(Args a, Dims d) {
     __syncthreads();
     const float2* res = fft_lines(x, y, d.row, tw, nl, true);
     float al = 1.f, r2n = 1.f, div = 1.f;
-    if constexpr (MODE == RI_ITER || MODE == RI_INIT || MODE == RI_TRAIN) {
+    if constexpr (MODE == RI_ITER || MODE == RI_INIT || MODE == RI_TRAIN || MODE == RI_TRAINF) {
         al = a.alpha(g);
-        if (!((MODE == RI_ITER || MODE == RI_TRAIN) && a.last)) r2n = a.rho2n(g);
+        if (!((MODE == RI_ITER || MODE == RI_TRAIN || MODE == RI_TRAINF) && a.last)) r2n = a.rho2n(g);
     }
     if constexpr (MODE == RI_RL_FINAL) div = a.otf[(size_t)g * K * H].x;  // conv(Ht, ones) = H(0,0)
     const bool poisson = a.llh == GD_LLH_POISSON;
@@ -632,6 +706,15 @@ __global__ __launch_bounds__(kThreads) void k_gen_ri(Args a, Dims d) {
             }
             continue;
         }
+        if constexpr (MODE == RI_PSF_BWD) {
+            // adjoint of gpsf: image pixel (r, c) is psf pixel ((r + h/2) mod H, (c + pw/2) mod W) inside the window
+            const int pw = a.pw ? a.pw : a.h;
+            int i = r + (a.h >> 1), jj = c + (pw >> 1);
+            if (i >= H) i -= H;
+            if (jj >= W) jj -= W;
+            if (i < a.h && jj < pw) a.o0[((size_t)g * a.h + i) * pw + jj] = X;
+            continue;
+        }
         const size_t pix = ((size_t)g * H + r) * W + c;
         if constexpr (MODE == RI_ITER) {
             // models/Unrolled_ADMM.py:207-215 (x = image 0, conv(H, x) = image 1)
@@ -647,12 +730,13 @@ __global__ __launch_bounds__(kThreads) void k_gen_ri(Args a, Dims d) {
                 a.o1[pix] = vn - u2;
                 a.o2[pix] = X + u1;                                      // next denoiser input
             }
-        } else if constexpr (MODE == RI_TRAIN) {
+        } else if constexpr (MODE == RI_TRAIN || MODE == RI_TRAINF) {
             // RI_ITER out of place: u1 (a1), w (a2) read-only; u1' -> o0, w' -> o1, zin' -> o2, vt -> o3 (saved)
             const float2 v1 = res[(pb + (rr >> 1)) * W + c];
             const float hx = (rr & 1) ? v1.y : v1.x;
             if (a.last) {
                 a.o2[pix] = poisson ? X * al : X;
+                if constexpr (MODE == RI_TRAINF) a.o3[pix] = X;  // x in the vt slot: d(x alpha)/dalpha
             } else {
                 const float u1 = (a.a1[pix] + X) - a.a0[pix];
                 const float u2 = hx - a.a2[pix];
@@ -834,6 +918,14 @@ struct GOps {
         GD_TRY(Lc::col<C_INV>(a, st));
         return Lc::ri<RI_OUT1>(a, st);
     }
+    static int psf_to_otf_bwd(Args a, hipStream_t st) {
+        GD_TRY(Lc::col<C_OTF_BWD>(a, st));
+        return Lc::ri<RI_PSF_BWD>(a, st);
+    }
+    static int conv_bwd_otf(Args a, hipStream_t st) {
+        GD_TRY(Lc::rf<RF_TWO>(a, st));
+        return Lc::col<C_XCORR>(a, st);
+    }
     static int admm_init(Args a0, hipStream_t st0) {
         // Poisson: a.o0 = u1, a.o1 = w, a.o2 = zin (x0); 80^2 / 112^2 in one launch (k_pois_small_init)
         if (GD_POIS_SMALL && g_fused_init && a0.gH == a0.gW && (a0.gH == 80 || a0.gH == 112) && a0.pw == 0)
@@ -909,6 +1001,20 @@ struct GOps {
         return chunks(a0, st0, [&](const Args& a, hipStream_t st) {
             GD_TRY(Lc::rf<RF_TRAIN_BWD>(a, st));
             GD_TRY(Lc::col<C_TRAIN_BWD>(a, st));
+            return Lc::ri<RI_TRAIN_BWD>(a, st);
+        });
+    }
+    static int train_iter_full(Args a0, hipStream_t st0) {
+        return chunks(a0, st0, [&](const Args& a, hipStream_t st) {
+            GD_TRY(Lc::rf<RF_ITER>(a, st));
+            GD_TRY(Lc::col<C_TRAINF>(a, st));
+            return Lc::ri<RI_TRAINF>(a, st);
+        });
+    }
+    static int train_iter_full_bwd(Args a0, hipStream_t st0) {
+        return chunks(a0, st0, [&](const Args& a, hipStream_t st) {
+            GD_TRY(Lc::rf<RF_TRAINF_BWD>(a, st));
+            GD_TRY(Lc::col<C_TRAINF_BWD>(a, st));
             return Lc::ri<RI_TRAIN_BWD>(a, st);
         });
     }

@@ -54,6 +54,13 @@ SIGNATURES = {
                                 _P, _P, _P, _P]),
     "gd_admm_train_iter_backward": (_I, [_P, _P, _P, _P, _P, _LL, _P, _LL, _P, _LL, _P, _LL, _I, _I, _I, _I, _I, _P,
                                          _P, _P, _P, _P, _P, _P, _P]),
+    "gd_admm_train_full_saved_bytes": (_SZ, [_I, _I, _I]),
+    "gd_admm_train_iter_full": (_I, [_P, _P, _P, _P, _P, _LL, _P, _LL, _P, _LL, _P, _LL, _I, _I, _I, _I, _I, _P, _P,
+                                     _P, _P, _P, _P, _P]),
+    "gd_admm_train_iter_full_backward": (_I, [_P, _P, _P, _P, _P, _LL, _P, _LL, _P, _LL, _P, _LL, _I, _I, _I, _I, _I,
+                                              _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gd_psf_to_otf_backward": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "gd_conv_fft_batch_backward_otf": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "gd_wiener": (_I, [_P, _P, _LL, _I, _I, _P, _LL, _P, _I, _I, _I, _P, _P]),
     "gd_richardson_lucy": (_I, [_P, _P, _LL, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
     "gd_tikhonov": (_I, [_P, _P, _LL, _I, _I, _P, _LL, _P, _LL, _P, _LL, _P, _I, _I, _I, _P, _P]),

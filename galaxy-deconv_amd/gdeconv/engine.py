@@ -121,8 +121,42 @@ def supported(H, W):
     return int(_lib.load().gd_supported_size(H, W))
 
 
+class _PsfToOtfFn(torch.autograd.Function):
+    """``psf_to_otf_half`` with its HIP adjoint (gd_psf_to_otf_backward): the OTF gradient, in the convention of
+    ``include/gdeconv.h`` (torch's own for a complex tensor), back to the PSF pixels."""
+
+    @staticmethod
+    def forward(ctx, psf, N, H, W):
+        ctx.meta = (tuple(psf.shape), psf.dtype, N, H, W)
+        return _psf_to_otf_raw(psf.detach(), N, H, W)
+
+    @staticmethod
+    def backward(ctx, g):
+        shape, dtype, N, H, W = ctx.meta
+        dev = g.device
+        lib = _lib.load()
+        g = g.to(torch.complex64).contiguous()
+        with _on(dev):
+            gp = torch.empty(N, 1, shape[2], shape[3], dtype=torch.float32, device=dev)
+            _lib.check(lib.gd_psf_to_otf_backward(g.data_ptr(), shape[2], shape[3], N, H, W, gp.data_ptr(),
+                                                  workspace(N, H, W, dev).data_ptr(), _stream(dev)),
+                       "gd_psf_to_otf_backward")
+        if shape[0] != N:
+            gp = gp.sum(0, keepdim=True)   # one PSF shared by the batch
+        return gp.to(dtype), None, None, None
+
+
 def psf_to_otf_half(psf, N, H, W):
-    """Half-spectrum OTF [N, W//2+1, H] of ``psf_to_otf`` (utils/utils_torch.py:79-92)."""
+    """Half-spectrum OTF [N, W//2+1, H] of ``psf_to_otf`` (utils/utils_torch.py:79-92).  Differentiable in ``psf``
+    when it requires grad (HIP adjoint); otherwise one engine call and no graph."""
+    if torch.is_grad_enabled() and psf.requires_grad:
+        _require_device(psf)
+        _psf(psf, N, H)
+        return _PsfToOtfFn.apply(psf, N, H, W)
+    return _psf_to_otf_raw(psf, N, H, W)
+
+
+def _psf_to_otf_raw(psf, N, H, W):
     dev = _require_device(psf)
     lib = _lib.load()
     with _on(dev):
@@ -134,10 +168,51 @@ def psf_to_otf_half(psf, N, H, W):
     return otf
 
 
+class _ConvHalfFn(torch.autograd.Function):
+    """``conv_half`` with HIP adjoints: the gradient to x is the convolution with ``conj`` flipped, the gradient to
+    the OTF the cross spectrum of gd_conv_fft_batch_backward_otf (summed over the batch for a shared OTF)."""
+
+    @staticmethod
+    def forward(ctx, otf_half, x, conj):
+        ctx.save_for_backward(otf_half.detach(), x.detach())
+        ctx.conj = bool(conj)
+        ctx.x_meta = (tuple(x.shape), x.dtype)
+        return _conv_half_raw(otf_half.detach(), x.detach(), conj)
+
+    @staticmethod
+    def backward(ctx, g):
+        otf_half, x = ctx.saved_tensors
+        g = _img(g, "grad")
+        gx = gotf = None
+        if ctx.needs_input_grad[1]:
+            gx = _conv_half_raw(otf_half, g, not ctx.conj).reshape(ctx.x_meta[0]).to(ctx.x_meta[1])
+        if ctx.needs_input_grad[0]:
+            dev = g.device
+            lib = _lib.load()
+            xf = _img(x, "x")
+            N, _, H, W = xf.shape
+            with _on(dev):
+                gotf = empty_otf(N, H, W, dev)
+                _lib.check(lib.gd_conv_fft_batch_backward_otf(xf.data_ptr(), g.data_ptr(), int(ctx.conj), N, H, W,
+                                                              gotf.data_ptr(), workspace(N, H, W, dev).data_ptr(),
+                                                              _stream(dev)), "gd_conv_fft_batch_backward_otf")
+            if otf_half.shape[0] != N:
+                gotf = gotf.sum(0, keepdim=True)
+        return gotf, gx, None
+
+
 def conv_half(otf_half, x, conj=False):
     """``conv_fft_batch(H, x)`` (utils/utils_torch.py:46-50) with H given as a half-spectrum OTF
     complex64 [1|N, W//2+1, H]; a 1-galaxy H applies to every image, as the reference's
-    ``fftn(x) * H`` broadcasts a [1,1,H,W] H."""
+    ``fftn(x) * H`` broadcasts a [1,1,H,W] H.  Differentiable in ``x`` and in the OTF when either requires grad
+    (HIP adjoints); otherwise one engine call and no graph."""
+    if torch.is_grad_enabled() and (x.requires_grad or otf_half.requires_grad):
+        _require_device(x, otf_half)
+        return _ConvHalfFn.apply(otf_half, x, conj)
+    return _conv_half_raw(otf_half, x, conj)
+
+
+def _conv_half_raw(otf_half, x, conj=False):
     dev = _require_device(x, otf_half)
     lib = _lib.load()
     x = _img(x, "x")
@@ -788,9 +863,16 @@ class ADMMTrainState:
     """What one differentiable ``Unrolled_ADMM`` forward shares between its iterations
     (models/Unrolled_ADMM.py:177-196): the half-spectrum OTF, ``x0 = clamp(init_l2)`` and ``hx0 = conv_fft_batch(H,
     x0)`` (gd_admm_train_init, computed at construction), y, alpha and the likelihood.  None of them carries a
-    gradient.  The iteration state itself (zin, u1, w = v - u2) lives in the autograd graph: ``admm_train_iter``."""
+    gradient.  The iteration state itself (zin, u1, w = v - u2) lives in the autograd graph: ``admm_train_iter``.
 
-    def __init__(self, y, psf, alpha, llh):
+    ``input_grads=True`` keeps y, alpha and the OTF in the graph as well: the OTF comes from the differentiable
+    ``psf_to_otf_half``, the init is composed of differentiable pieces (init_l2's spectrum is the X update with A = 0,
+    w = y+, rho1 = 1, rho2 = 1 / alpha; the clamp is elementwise; ``hx0 = conv_half(otf, x0)``), and
+    ``admm_train_iter`` routes to gd_admm_train_iter_full and its adjoint, whose per-iteration gradients to y, alpha
+    and the OTF autograd sums.  y+ = max(y, 0) passes gradient where y > 0 only."""
+
+    def __init__(self, y, psf, alpha, llh, input_grads=False):
+        self.input_grads = bool(input_grads)
         self.dev = _require_device(y, psf, alpha)
         self.lib = _lib.load()
         self.y = _img(y.detach(), "y")
@@ -804,6 +886,9 @@ class ADMMTrainState:
         self.saved_bytes = int(self.lib.gd_admm_train_saved_bytes(max(self.N, 1), self.H, self.W))
         self.K = self.W // 2 + 1
         k = self.psf
+        if self.input_grads:
+            self._init_input_grads(y, psf, alpha)
+            return
         with _on(self.dev):
             self.alpha, self.alpha_s = _galaxy_scalar(alpha.detach() if torch.is_tensor(alpha) else alpha, self.N,
                                                       "alpha", self.dev)
@@ -814,14 +899,37 @@ class ADMMTrainState:
                 self.alpha_s, self.N, self.H, self.W, self.otf.data_ptr(), self.x0.data_ptr(), self.hx0.data_ptr(),
                 workspace(self.N, self.H, self.W, self.dev).data_ptr(), _stream(self.dev)), "gd_admm_train_init")
 
+    def _init_input_grads(self, y, psf, alpha):
+        """The ``input_grads=True`` construction: every quantity twice, detached for the engine's raw pointers and
+        in the graph (``*_in``) for autograd."""
+        self.full_saved_bytes = int(self.lib.gd_admm_train_full_saved_bytes(max(self.N, 1), self.H, self.W))
+        with _on(self.dev):
+            self.alpha, self.alpha_s = _galaxy_scalar(alpha.detach() if torch.is_tensor(alpha) else alpha, self.N,
+                                                      "alpha", self.dev)
+        self.y_in = y
+        self.alpha_in = alpha if torch.is_tensor(alpha) else self.alpha
+        self.otf_in = psf_to_otf_half(psf, self.N, self.H, self.W)
+        self.otf = self.otf_in.detach()
+        # y+ with no gradient at y <= 0 (the engine's choice at y == 0, see gdeconv.h), alpha against images
+        y4 = y.float()
+        self.yp_in = torch.where(y4 > 0, y4, torch.zeros_like(y4))
+        self.alpha4_in = self.alpha_in.float().reshape(-1, 1, 1, 1)
+        zero = torch.zeros_like(self.y)
+        x0raw = _ADMMTrainIterFullFn.apply(zero, zero, self.yp_in, 1.0, 1.0 / self.alpha4_in, None, None, None,
+                                           self.otf_in, self, True, _lib.GD_LLH["Gaussian"])
+        self.x0 = x0raw.clamp(0.0, 1.0)
+        self.hx0 = conv_half(self.otf_in, self.x0)
+
     def alpha4(self):
         """alpha as it broadcasts against [N,1,H,W] images."""
+        if self.input_grads:
+            return self.alpha4_in
         return self.alpha.view(-1, 1, 1, 1)
 
     def w0(self, rho2_first):
         """w_0 = V(hx0; rho2[0]) (u2 = 0), differentiable in ``rho2_first``: the first V step (:207), once per
         forward, as PyTorch elementwise ops."""
-        yp, al = self.y.clamp_min(0.0), self.alpha4()
+        yp, al = (self.yp_in if self.input_grads else self.y.clamp_min(0.0)), self.alpha4()
         if self.llh_name == "Poisson":
             t1 = rho2_first * self.hx0 - al
             return 0.5 * (1 / rho2_first) * (-t1 + torch.sqrt(t1 ** 2 + 4 * yp * rho2_first))
@@ -903,11 +1011,86 @@ class _ADMMTrainIterFn(torch.autograd.Function):
                 gw if ctx.needs_input_grad[2] else None, grho[0], grho[1], grho[2], None, None)
 
 
+class _ADMMTrainIterFullFn(torch.autograd.Function):
+    """``_ADMMTrainIterFn`` with gradients to y, alpha and the OTF as well (gd_admm_train_iter_full and
+    gd_admm_train_iter_full_backward).  Each call owns its saved buffer (two half spectra and one image)."""
+
+    @staticmethod
+    def forward(ctx, z, u1, w, rho1, rho2, rho2_next, y, alpha, otf, st, last, llh):
+        N, H, W, dev = st.N, st.H, st.W, st.dev
+        shape = tuple(st.y.shape)
+        ins = []
+        for t, name in ((z, "z"), (u1, "u1"), (w, "w")):
+            t = _img(t.detach(), name)
+            if tuple(t.shape) != shape or t.device != dev:
+                raise ValueError(f"{name} must be {shape} on {dev}, got {tuple(t.shape)} on {t.device}")
+            ins.append(t)
+        r1 = st.rho(rho1)
+        r2 = st.rho(rho2)
+        r2n = st.rho(rho2_next) if not last else (None, None, 0)
+        with _on(dev):
+            zin = torch.empty_like(st.y)
+            u1o = None if last else torch.empty_like(st.y)
+            wo = None if last else torch.empty_like(st.y)
+            saved = torch.empty(st.full_saved_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(st.lib.gd_admm_train_iter_full(
+                st.y.data_ptr(), ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(), st.alpha.data_ptr(),
+                st.alpha_s, r1[1], r1[2], r2[1], r2[2], r2n[1], r2n[2], llh, int(last), N, H, W,
+                st.otf.data_ptr(), zin.data_ptr(), None if last else u1o.data_ptr(), None if last else wo.data_ptr(),
+                saved.data_ptr(), workspace(N, H, W, dev).data_ptr(), _stream(dev)), "gd_admm_train_iter_full")
+        ctx.st, ctx.last, ctx.llh, ctx.saved, ctx.rhos = st, last, llh, saved, (r1, r2, r2n)
+        ctx.rho_meta = [(t.shape, t.dtype) if torch.is_tensor(t) else None for t in (rho1, rho2, rho2_next)]
+        ctx.in_meta = [(t.shape, t.dtype) if torch.is_tensor(t) else None for t in (y, alpha)]
+        return zin if last else (zin, u1o, wo)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        st, last = ctx.st, ctx.last
+        N, H, W, K, dev = st.N, st.H, st.W, st.K, st.dev
+        r1, r2, r2n = ctx.rhos
+        g = [None if t is None else t.float().contiguous() for t in grads]
+        with _on(dev):
+            gz, gu1, gw, gy = (torch.empty_like(st.y) for _ in range(4))
+            part = torch.empty(N, 2 * K + H, dtype=torch.float32, device=dev)
+            apart = torch.empty(N, H, dtype=torch.float32, device=dev)
+            gotf = empty_otf(N, H, W, dev)
+            _lib.check(st.lib.gd_admm_train_iter_full_backward(
+                g[0].data_ptr(), None if last else g[1].data_ptr(), None if last else g[2].data_ptr(),
+                st.y.data_ptr(), st.alpha.data_ptr(), st.alpha_s, r1[1], r1[2], r2[1], r2[2], r2n[1], r2n[2], ctx.llh,
+                int(last), N, H, W, st.otf.data_ptr(), ctx.saved.data_ptr(), gz.data_ptr(), gu1.data_ptr(),
+                gw.data_ptr(), part.data_ptr(), gotf.data_ptr(), gy.data_ptr(), apart.data_ptr(),
+                workspace(N, H, W, dev).data_ptr(), _stream(dev)), "gd_admm_train_iter_full_backward")
+        groups = (part[:, :K], part[:, K:2 * K], part[:, 2 * K:])
+
+        def scalar_grad(gg, meta):   # per-galaxy sums -> the shape the scalar came in (a shared one: summed)
+            shp, dt = meta
+            n_el = 1
+            for s in shp:
+                n_el *= s
+            gg = gg.sum() if n_el == 1 else gg
+            return gg.reshape(shp).to(dt)
+
+        grho = [scalar_grad(groups[i].sum(1), meta) if meta is not None and ctx.needs_input_grad[3 + i] else None
+                for i, meta in enumerate(ctx.rho_meta)]
+        g_y = g_al = None
+        if ctx.in_meta[0] is not None and ctx.needs_input_grad[6]:
+            g_y = gy.reshape(ctx.in_meta[0][0]).to(ctx.in_meta[0][1])
+        if ctx.in_meta[1] is not None and ctx.needs_input_grad[7]:
+            g_al = scalar_grad(apart.sum(1), ctx.in_meta[1])
+        return (gz if ctx.needs_input_grad[0] else None, gu1 if ctx.needs_input_grad[1] else None,
+                gw if ctx.needs_input_grad[2] else None, grho[0], grho[1], grho[2], g_y, g_al,
+                gotf if ctx.needs_input_grad[8] else None, None, None, None)
+
+
 def admm_train_iter(st, z, u1, w, rho1, rho2, rho2_next, last):
     """One differentiable loop body of ``Unrolled_ADMM`` (models/Unrolled_ADMM.py:199-215) after the denoiser
     returned ``z``: ``(zin', u1', w')``, or the output x (times alpha for Poisson) when ``last``.  Gradients flow to
     z, u1, w and the rhos ([N,1,1,1] views or 0-dim entries of a shared schedule, whose gradient is the sum over
-    galaxies); ``st`` is the forward's ``ADMMTrainState``.  ``rho2_next`` is ignored when ``last``."""
+    galaxies); ``st`` is the forward's ``ADMMTrainState``.  ``rho2_next`` is ignored when ``last``.  With
+    ``ADMMTrainState(..., input_grads=True)`` gradients also flow to y, alpha and the OTF (hence the PSF)."""
+    if st.input_grads:
+        return _ADMMTrainIterFullFn.apply(z, u1, w, rho1, rho2, None if last else rho2_next, st.y_in, st.alpha_in,
+                                          st.otf_in, st, bool(last), st.llh)
     return _ADMMTrainIterFn.apply(z, u1, w, rho1, rho2, None if last else rho2_next, st, bool(last))
 
 

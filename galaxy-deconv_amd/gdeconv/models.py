@@ -30,6 +30,13 @@ parameter gradients can be dropped that way: an input ``y`` / ``kernel`` / ``alp
   supported size), so the output's graph reaches ``Z``, ``init`` and ``rho1_iters`` / ``rho2_iters``.  Under
   ``torch.no_grad()`` or with nothing to differentiate it is the parent's fast path.  No gradient to
   ``y`` / ``kernel`` / ``alpha`` (such inputs raise).
+* ``DifferentiableUnrolledADMM(...)`` - ``TrainableUnrolledADMM`` that is also differentiable in ``y``, ``kernel`` and
+  ``alpha`` (whichever require grad), the path through the SubNet included: the OTF through the HIP adjoint of
+  ``psf_to_otf``, every loop body through gd_admm_train_iter_full and its adjoint (OTF gradient accumulated over the
+  iterations, V-step derivatives in y and alpha).  Shared ``[1,1,h,w]`` PSFs and scalar alphas get gradients of their
+  own shape.  With no input that requires grad it is ``TrainableUnrolledADMM`` exactly.  Out of scope: gradients
+  through ``Wiener``, ``Richard_Lucy``, ``Tikhonov`` and to the inputs of ``UnrolledADMMGaussian``, and the fused
+  one-workgroup-per-galaxy kernels (training always runs the row / column chains).
 """
 import warnings
 
@@ -174,6 +181,45 @@ class TrainableUnrolledADMM(Unrolled_ADMM):
                                                 pick(rho2_iters, it + 1), False)
 
 
+class DifferentiableUnrolledADMM(TrainableUnrolledADMM):
+    """``TrainableUnrolledADMM`` that is also differentiable in its inputs, as the reference module is: gradients
+    reach the parameters and whichever of ``y``, ``kernel``, ``alpha`` require grad (PSF-error sensitivity, noise
+    propagation, fitting PSF or flux parameters through the network).  Same constructor, attributes and
+    ``state_dict`` keys.  The OTF comes from the differentiable ``engine.psf_to_otf_half``, every loop body runs
+    gd_admm_train_iter_full and its HIP adjoint (``engine.ADMMTrainState(..., input_grads=True)``), and the SubNet
+    takes its PyTorch path (in eval mode too: the engine SubNet has no backward), so the path through the rhos is
+    included.  A shared ``[1,1,h,w]`` PSF and a scalar or ``[N,1,1,1]`` alpha are supported; each gradient has its
+    input's shape.  With no input that requires grad it is exactly ``TrainableUnrolledADMM`` (same calls, bit-identical
+    results); under ``torch.no_grad()`` it is the inference path."""
+
+    def forward(self, y, kernel, alpha):
+        if not (torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (y, kernel, alpha))):
+            return super().forward(y, kernel, alpha)
+        st = engine.ADMMTrainState(y, kernel, alpha, self.llh, input_grads=True)   # rejects CPU tensors
+        n = self.n
+        if n == 0:
+            return st.x0 * st.alpha4() if self.llh == "Poisson" else st.x0
+        use = self.init.use_engine if self.subnet else None
+        if self.subnet:
+            self.init.use_engine = False   # the engine SubNet has no backward: PyTorch ops, in eval mode too
+        try:
+            rho1_iters, rho2_iters = self.rhos(kernel, alpha)
+        finally:
+            if self.subnet:
+                self.init.use_engine = use
+
+        def pick(r, i):   # models/Unrolled_ADMM.py:201-206
+            return r[:, :, :, i].view(-1, 1, 1, 1) if r.dim() == 4 else r[i]
+
+        zin, u1, w = st.x0, torch.zeros_like(st.y), st.w0(pick(rho2_iters, 0))
+        for it in range(n):
+            z = self.Z(zin)
+            if it == n - 1:
+                return engine.admm_train_iter(st, z, u1, w, pick(rho1_iters, it), pick(rho2_iters, it), None, True)
+            zin, u1, w = engine.admm_train_iter(st, z, u1, w, pick(rho1_iters, it), pick(rho2_iters, it),
+                                                pick(rho2_iters, it + 1), False)
+
+
 class Wiener(nn.Module):
     def forward(self, y, psf, alpha):
         return engine.wiener(y, psf, alpha)
@@ -308,6 +354,6 @@ class Tikhonet(nn.Module):
         return x * alpha
 
 
-__all__ = ["Unrolled_ADMM", "TrainableUnrolledADMM", "UnrolledADMMGaussian", "XUpdateGaussian", "Wiener",
+__all__ = ["Unrolled_ADMM", "TrainableUnrolledADMM", "DifferentiableUnrolledADMM", "UnrolledADMMGaussian", "XUpdateGaussian", "Wiener",
            "Richard_Lucy", "Tikhonov",
            "Tikhonet", "laplacian_kernel"]

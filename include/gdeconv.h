@@ -30,6 +30,9 @@
  *   gd_admm_train_init  models/Unrolled_ADMM.py:181-196 + init_l2 :170-175 and conv_fft_batch(H, x0) of :207, kept as images
  *   gd_admm_train_iter  models/Unrolled_ADMM.py:199-215 loop body, out of place, saving what its adjoint needs
  *   gd_admm_train_iter_backward  the adjoint of that body (autograd for training / fine-tuning Unrolled_ADMM)
+ *   gd_admm_train_iter_full / _full_backward  the same body and adjoint with gradients to y, the OTF and alpha as well
+ *   gd_psf_to_otf_backward / gd_conv_fft_batch_backward_otf  the adjoints of psf_to_otf and of conv_fft_batch in H
+ *                       (the reference module is differentiable in y, kernel and alpha: torch.autograd through it)
  *   gd_wiener           models/Wiener.py:10-20       Wiener.forward(y, psf, alpha)
  *   gd_richardson_lucy  models/Richard_Lucy.py:10-24 Richard_Lucy(n_iters).forward(y, psf)
  *   gd_tikhonov         models/Tikhonet.py:15-31     Tikhonov(filter).forward(y, psf, alpha, lam)
@@ -51,7 +54,9 @@ extern "C" {
 #endif
 
 #define GD_ABI_VERSION 5  /* 5: strict 0 / 1 fused-path setters, capture pipelining opt-in (mode 1 gone);
-                             still 5, purely additive: gd_admm_train_saved_bytes / _init / _iter / _iter_backward */
+                             still 5, purely additive: gd_admm_train_saved_bytes / _init / _iter / _iter_backward;
+                             gd_psf_to_otf_backward, gd_conv_fft_batch_backward_otf, gd_admm_train_full_saved_bytes,
+                             gd_admm_train_iter_full / _full_backward (input gradients) */
 
 #define GD_OK 0
 #define GD_ERR_ARG (-1)
@@ -189,7 +194,7 @@ int gd_admm_tail_supported(int N, int H, int W, int llh);
  *   (1/HW) sum_k Re(conj(Q) E) (half-spectrum bins other than kx = 0, W/2 twice), a row-inverse epilogue
  *   g_z = rho1 F^-1 Q - (g_zin + g_u1'), g_u1 = -g_z, g_w = g_w' - g_vt + rho2 F^-1(H Q).  No atomics: the same
  *   inputs give bit-identical gradients.  Outputs must not alias inputs or each other (GD_ERR_ARG).
- * No gradient flows to y, the PSF or alpha.  All three run the row / column chains whatever gd_set_fused_* and
+ * No gradient flows to y, the PSF or alpha from these calls (gd_admm_train_iter_full below adds them).  All three run the row / column chains whatever gd_set_fused_* and
  * gd_set_fused_min_batch say, and honour gd_set_chunk_bytes / gd_set_pipeline_streams.  ws: gd_workspace_bytes.
  * All validation precedes any HIP call. */
 size_t gd_admm_train_saved_bytes(int N, int H, int W);
@@ -207,6 +212,82 @@ int gd_admm_train_iter_backward(const float* g_zin_or_out, const float* g_u1_out
                                 long long rho2_next_stride, int llh, int last, int N, int H, int W, const void* otf_half,
                                 const void* saved, float* g_z, float* g_u1, float* g_w, float* g_rho_part, void* ws,
                                 void* stream);
+
+/* Training with INPUT gradients: the same body as gd_admm_train_iter, differentiable also in y, the OTF and alpha
+ * (PSF-error sensitivity, noise propagation, fitting PSF or flux parameters through the unrolled network).  The two
+ * calls above are unchanged and still carry no such gradient; these are their supersets.
+ *
+ * gd_admm_train_iter_full: gd_admm_train_iter's arguments and outputs (the same row / column / row chain; only what
+ *   the column pass and the last row pass keep differs; the outputs agree with gd_admm_train_iter's to rounding, 1e-6
+ *   normwise, not bit for bit: the kernels are separate instantiations and contract their multiply-adds
+ *   differently).  saved: gd_admm_train_full_saved_bytes(N, H,
+ *   W) = 2 x N (W/2+1) H 8 bytes, the half spectra X and F(w) (the OTF gradient needs them apart; E = conj(H) F(w) - X
+ *   is re-formed in the backward), plus ONE image, N H W 4 bytes: vt, or x itself when last.  Two half spectra plus one
+ *   image against gd_admm_train_iter's one plus one: 12 instead of 8 bytes per pixel; re-computing F(w) in the backward
+ *   instead would cost a third image in its row-forward pass and a third column transform in every backward.
+ * gd_admm_train_iter_full_backward: gd_admm_train_iter_backward's arguments and outputs (g_z, g_u1, g_w, g_rho_part,
+ *   same layout), plus
+ *     g_otf_half   complex64 [N][W/2+1][H], the OTF gradient of this body in the convention below.  With A = F(z - u1),
+ *                  Wf = F(w), D = rho1 |H|^2 + rho2, X = (rho1 A + rho2 conj(H) Wf) / D and the column pass's
+ *                  Q = (F(g_x) + conj(H) F(g_hx)) / D:  g_H = F(g_hx) conj(X) + rho2 conj(Q) Wf - 2 rho1 H Re(Q conj(X)),
+ *                  stored as c g_H / (H W), c = 1 at kx = 0, W/2 and 2 elsewhere;
+ *     g_y          fp32 [N][H][W] = g_w' dV/dy+ where y > 0 and 0 elsewhere (all zero when last).  y+ = max(y, 0)
+ *                  passes its gradient only where y > 0: at y == 0 exactly this is 0, where torch.max(y, 0) would pass
+ *                  half of it;
+ *     g_alpha_part fp32 [N][H]: per galaxy one part of dL/dalpha per block of rows (the block's other rows zero), in a
+ *                  fixed order like the rho2_next parts; the caller sums them per galaxy (and over galaxies for a shared
+ *                  alpha).  They hold sum g_w' dV/dalpha and, on the last Poisson body, sum g_out x of the output
+ *                  scaling x alpha.
+ *   V step: Gaussian dV/dy+ = 1 / (alpha (1 + rho)), dV/dalpha = -y+ / (alpha^2 (1 + rho)); Poisson, t = rho vt - alpha,
+ *   s = sqrt(t^2 + 4 y+ rho): dV/dy+ = 1 / s, dV/dalpha = (s - t) / (2 rho s), s - t formed without cancellation.
+ *   Three passes as gd_admm_train_iter_backward: the row-forward prologue also writes g_y and the alpha parts, the
+ *   column pass also writes g_otf_half, the row-inverse epilogue is the same kernel.  No atomics: the same inputs give
+ *   bit-identical gradients, chunked or not.  Outputs must not alias inputs or each other (GD_ERR_ARG).
+ * Both run the row / column chains whatever gd_set_fused_* say and honour gd_set_chunk_bytes /
+ * gd_set_pipeline_streams; every supported size, both likelihoods; N = 0 is valid; all validation precedes any HIP call.
+ * The init needs no entry point of its own: init_l2's spectrum is the X update with A = 0, w = y+, rho1 = 1,
+ * rho2 = 1 / alpha (llh = Gaussian, last != 0), the clamp is elementwise and H x0 is gd_conv_fft_batch. */
+size_t gd_admm_train_full_saved_bytes(int N, int H, int W);
+int gd_admm_train_iter_full(const float* y, const float* z, const float* u1, const float* w, const float* alpha,
+                            long long alpha_stride, const float* rho1, long long rho1_stride, const float* rho2,
+                            long long rho2_stride, const float* rho2_next, long long rho2_next_stride, int llh, int last,
+                            int N, int H, int W, const void* otf_half, float* zin_or_out, float* u1_out, float* w_out,
+                            void* saved, void* ws, void* stream);
+int gd_admm_train_iter_full_backward(const float* g_zin_or_out, const float* g_u1_out, const float* g_w_out,
+                                     const float* y, const float* alpha, long long alpha_stride, const float* rho1,
+                                     long long rho1_stride, const float* rho2, long long rho2_stride,
+                                     const float* rho2_next, long long rho2_next_stride, int llh, int last, int N, int H,
+                                     int W, const void* otf_half, const void* saved, float* g_z, float* g_u1, float* g_w,
+                                     float* g_rho_part, void* g_otf_half, float* g_y, float* g_alpha_part, void* ws,
+                                     void* stream);
+
+/* Input gradients: the adjoints that carry a loss gradient from an OTF back to the PSF, and from a convolution's
+ * output to its OTF.
+ *
+ * OTF-GRADIENT CONVENTION.  An OTF gradient g_otf_half is complex64 [N][W/2+1][H], transposed like the OTF itself.
+ * For a real perturbation of whatever produced the OTF,
+ *     dL = sum over the STORED bins (kx <= W/2, every ky) of Re(conj(g_otf_half) dOTF_half),
+ * the plain real inner product over the stored entries (what torch.autograd means by the gradient of a complex
+ * tensor).  Every producer folds the mirrored bins' contributions (kx > W/2) into the stored bin: columns other than
+ * kx = 0 and, for even W, kx = W/2 count twice.
+ *
+ * gd_psf_to_otf_backward: the exact transpose of gd_psf_to_otf under that inner product: g_psf [N][h][w] =
+ *   sum over the stored bins of Re(g_otf_half exp(+2 pi i (kx c / W + ky r / H))) at the pixel (r, c) the circular
+ *   placement gives psf pixel (i, j) - an UNNORMALISED inverse real 2-D transform WITHOUT the Hermitian doubling,
+ *   gathered back through the placement.  Two passes: a column pass (columns other than kx = 0, W/2 halved, inverse
+ *   column transforms) and a row-inverse pass whose sink writes the h x w window.  One gradient per galaxy: for a
+ *   PSF shared by the batch (gd_psf_to_otf's psf_gstride = 0) the caller sums g_psf over the galaxies.
+ * gd_conv_fft_batch_backward_otf: the OTF gradient of out = gd_conv_fft_batch(otf, conj, x) given g_out = dL/dout:
+ *   g_otf_half = c F(g_out) conj(F(x)) / (H W)  (conj != 0: c conj(F(g_out)) F(x) / (H W)), c = 1 at kx = 0, W/2 and 2
+ *   elsewhere.  One row-forward pass over both images and one column pass.  One gradient per galaxy: for an OTF shared
+ *   by the batch the caller sums over the galaxies.  The gradient to x needs nothing new: it is gd_conv_fft_batch of
+ *   g_out with conj flipped.
+ * Both: ws = gd_workspace_bytes(N, H, W); outputs must not alias inputs or ws (GD_ERR_ARG); N = 0 is valid; all
+ * validation precedes any HIP call; no atomics, so the same inputs give bit-identical gradients. */
+int gd_psf_to_otf_backward(const void* g_otf_half, int h, int w, int N, int H, int W, float* g_psf, void* ws,
+                           void* stream);
+int gd_conv_fft_batch_backward_otf(const float* x, const float* g_out, int conj, int N, int H, int W, void* g_otf_half,
+                                   void* ws, void* stream);
 
 /* x = Re IFFT2(conj(H) FFT2(y) / (|H|^2 + 350/alpha)). */
 int gd_wiener(const float* y, const float* psf, long long psf_gstride, int h, int w, const float* alpha,

@@ -10,6 +10,13 @@ per path.  The two outputs and rho gradients are compared in the same run.  Prin
 likelihood) and writes them all to ``--out``.
 
     python tools/train_step_bench.py --out profiles/train_step_bench.json
+
+``--input-grads``: the same step with y, the PSF and alpha requiring grad as well (``DifferentiableUnrolledADMM``:
+gd_admm_train_iter_full and its adjoint, the HIP adjoints of psf_to_otf and conv_fft_batch) against the same
+``rfft2`` loop differentiating its inputs; the parameter-only engine step is re-measured in the same interleaved
+blocks, so the record also holds what the input gradients cost on top of it.
+
+    python tools/train_step_bench.py --input-grads --out profiles/train_step_bench_input_grads.json
 """
 import argparse
 import json
@@ -23,7 +30,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "galaxy-deconv_amd"))
 
-from gdeconv.models import TrainableUnrolledADMM  # noqa: E402
+from gdeconv.models import DifferentiableUnrolledADMM, TrainableUnrolledADMM  # noqa: E402
 from gdeconv.synth import make_batch  # noqa: E402
 
 
@@ -75,6 +82,7 @@ def main():
     ap.add_argument("--blocks", type=int, default=5, help="interleaved blocks per path (median reported)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--input-grads", action="store_true", help="y, psf and alpha require grad as well")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("train_step_bench needs a ROCm device (no CPU timing)")
@@ -87,7 +95,8 @@ def main():
         y, psf, alpha, _ = make_batch(N, L, h=min(48, L), seed=1, device=dev)
         R = torch.randn(y.shape, generator=torch.Generator().manual_seed(2)).to(dev)
         for llh in ("Poisson", "Gaussian"):
-            m = TrainableUnrolledADMM(n_iters=a.n_iters, llh=llh, subnet=False)
+            m = (DifferentiableUnrolledADMM if a.input_grads else TrainableUnrolledADMM)(
+                n_iters=a.n_iters, llh=llh, subnet=False)
             m.Z = ConvDenoiser()
             m = m.to(dev).train()
             with torch.no_grad():
@@ -95,11 +104,17 @@ def main():
                 m.rho1_iters.copy_(0.5 + torch.rand(a.n_iters, generator=g))
                 m.rho2_iters.copy_(0.5 + torch.rand(a.n_iters, generator=g))
 
-            def step(engine):
+            leaves = [t.clone().requires_grad_() for t in (y, psf, alpha)] if a.input_grads else []
+
+            def step(engine, inputs=a.input_grads):
                 m.zero_grad(set_to_none=True)
-                out = m(y, psf, alpha) if engine else torch_loop(y, psf, alpha, m.rho1_iters, m.rho2_iters, llh, m.Z)
+                for t in leaves:
+                    t.grad = None
+                yy, pp, aa = leaves if inputs else (y, psf, alpha)
+                out = m(yy, pp, aa) if engine else torch_loop(yy, pp, aa, m.rho1_iters, m.rho2_iters, llh, m.Z)
                 (out * R).sum().backward()
-                return out.detach(), m.rho1_iters.grad.clone(), m.rho2_iters.grad.clone()
+                return (out.detach(), m.rho1_iters.grad.clone(), m.rho2_iters.grad.clone(),
+                        *([t.grad.clone() for t in leaves] if inputs else []))
 
             def block(engine):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -110,20 +125,38 @@ def main():
                 e1.synchronize()
                 return e0.elapsed_time(e1) / a.steps
 
+            def block_params_only():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(a.steps):
+                    step(True, inputs=False)
+                e1.record()
+                e1.synchronize()
+                return e0.elapsed_time(e1) / a.steps
+
             for _ in range(a.warmup):
-                oe, g1e, g2e = step(True)
-                ot, g1t, g2t = step(False)
+                re_ = step(True)
+                rt_ = step(False)
+                if a.input_grads:
+                    step(True, inputs=False)
             rel = lambda p, q: float((p - q).abs().max() / q.abs().max())  # noqa: E731
-            agree = {"out": rel(oe, ot), "d_rho1": rel(g1e, g1t), "d_rho2": rel(g2e, g2t)}
-            te, tt = [], []
+            names = ["out", "d_rho1", "d_rho2"] + (["d_y", "d_psf", "d_alpha"] if a.input_grads else [])
+            agree = {k: rel(p, q) for k, p, q in zip(names, re_, rt_)}
+            te, tt, tp = [], [], []
             for _ in range(a.blocks):
                 te.append(block(True))
                 tt.append(block(False))
+                if a.input_grads:
+                    tp.append(block_params_only())
             rec = {"tool": "train_step_bench", "engine_rev": rev, "N": N, "H": L, "W": L, "llh": llh,
                    "n_iters": a.n_iters, "steps_per_block": a.steps, "blocks": a.blocks,
                    "engine_ms_per_step": statistics.median(te), "torch_rfft2_ms_per_step": statistics.median(tt),
                    "engine_ms_blocks": te, "torch_rfft2_ms_blocks": tt,
                    "speedup": statistics.median(tt) / statistics.median(te), "engine_vs_torch_max_rel": agree}
+            if a.input_grads:
+                rec.update({"input_grads": True, "engine_params_only_ms_per_step": statistics.median(tp),
+                            "engine_params_only_ms_blocks": tp,
+                            "input_grads_cost_ratio": statistics.median(te) / statistics.median(tp)})
             print(json.dumps(rec), flush=True)
             assert max(agree.values()) < 1e-3, f"the two paths disagree: {agree}"
             results.append(rec)
